@@ -23,6 +23,15 @@ agent (config 1: the whole dqn agent, parts.run_loop over raw 210x160 RGB
 frames through processors.atari, a 1M TransitionReplay, learning every 16
 frames once 5 % of it is full; K learner steps are timed, 16 K frames).
 
+A plain run sets up, warms up, times the K steps and prints the line.
+`--full` adds what takes runs of its own after the timed region: the
+per-phase times and the `roofline` they give, the stand-alone sampler
+launches, the MGSC meta-update and learn-frame timings, and `cpu_baseline`.
+`--dump-outputs DIR` writes what the last timed step left with its caller
+(q_tm1, td, loss, the drawn slots, the parameters and RMSProp moments) to
+DIR/<name>.npy on rank 0; the inputs are seeded, so two builds run with the
+same arguments can be compared array for array.
+
 Prints ONE JSON line on rank 0.
 """
 
@@ -349,6 +358,37 @@ def _run_ranks(n, argv, store_file, script, store_env):
   return 0
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together
+
+
+def dump_outputs(dirname, arrays):
+  """Writes {name: array or tensor} as dirname/<name>.npy, float64 kept,
+  everything else as float32.  An array above its share of DUMP_LIMIT_BYTES
+  is written as a fixed sample: the elements at sorted indices drawn without
+  replacement by default_rng(0), the same from run to run."""
+  os.makedirs(dirname, exist_ok=True)
+  share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+  for name, a in arrays.items():
+    if isinstance(a, torch.Tensor):
+      a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    if a.nbytes > share:
+      keep = np.sort(np.random.default_rng(0).choice(
+          a.size, share // a.itemsize, replace=False))
+      a = a.reshape(-1)[keep]
+    np.save(os.path.join(dirname, name + '.npy'), a)
+
+
+def learner_outputs(lrn, extra=None):
+  """What a step leaves with its caller, as host arrays (synchronises)."""
+  q_tm1, td, loss = lrn.fetch_outputs()
+  out = {'q_tm1': q_tm1, 'td': td, 'loss': loss, 'online': lrn.online,
+         'target': lrn.target, 'mu': lrn.mu, 'nu': lrn.nu}
+  out.update(extra or {})
+  return {k: v.detach().cpu().numpy() for k, v in out.items() if v is not None}
+
+
 def parse_args(argv=None):
   ap = argparse.ArgumentParser()
   ap.add_argument('--gpus', type=int, default=1)
@@ -368,8 +408,17 @@ def parse_args(argv=None):
                        'for a graph submission)')
   ap.add_argument('--target-period', type=int, default=2500)
   ap.add_argument('--stats-every', type=int, default=1000)
-  ap.add_argument('--profile-iters', type=int, default=100)
-  ap.add_argument('--cpu-seconds', type=float, default=20.0)
+  ap.add_argument('--full', action='store_true',
+                  help='after the timed steps also measure the per-phase '
+                       'times and roofline, the stand-alone samplers, the '
+                       'MGSC meta-update / learn frame and the CPU baseline')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write what the last timed step computed to '
+                       'DIR/<name>.npy (rank 0)')
+  ap.add_argument('--profile-iters', type=int, default=100,
+                  help='--full: launches per phase timing')
+  ap.add_argument('--cpu-seconds', type=float, default=20.0,
+                  help='--full: seconds of the CPU baseline (0: none)')
   ap.add_argument('--selftest-cpu', action='store_true',
                   help='orchestration self-test on CPU (gloo, no GPU, a '
                        'stand-in step): exercises rank launch, timing and '
@@ -467,6 +516,8 @@ def selftest_cpu(args, g, rem):
   warm = counters['steps']
   elapsed = _timed(reps, runner, args.steps, g, rem, lambda: None,
                    lead=args.lead_eager)
+  if args.dump_outputs and reps.rank == 0:
+    dump_outputs(args.dump_outputs, {'x': x})
   elapsed_max = reps.max_over_ranks(elapsed)
   per_rank = reps.gather_stats([counters['steps'] - warm, elapsed,
                                 counters['syncs'], counters['gathers']])
@@ -738,6 +789,44 @@ def _json_stdout():
   return out
 
 
+def dominant_phase_roofline(algo, wl, phases, sampler_ms):
+  """The `roofline` object of a --full line: the slowest phase launch
+  (HIP-event ms of lrn.profile / time_samplers) against its nearer roof."""
+  flops = phase_flops(algo, BATCH)
+  nbytes = phase_bytes(algo, BATCH)
+  timed_phases = dict(phases)
+  for k, v in sampler_ms.items():
+    if k in wl.sampler_bytes:  # HBM-bound samplers compete for the roofline
+      timed_phases[k] = v
+      flops[k] = 0
+      nbytes[k] = wl.sampler_bytes[k]
+  dom = max(timed_phases, key=timed_phases.get)
+  dom_ms = timed_phases[dom]
+  # The bound is whichever roof the kernel sits closer to.
+  tflops = flops[dom] / (dom_ms * 1e-3) / 1e12
+  gbs = nbytes[dom] / (dom_ms * 1e-3) / 1e9
+  mfma_frac = tflops / F32_MFMA_PEAK_TFLOPS
+  hbm_frac = gbs / HBM_PEAK_GBS
+  if mfma_frac >= hbm_frac:
+    roof = {'bound': 'mfma', 'achieved': round(tflops, 3),
+            'peak': F32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+            'frac': round(mfma_frac, 4)}
+  else:
+    roof = {'bound': 'hbm', 'achieved': round(gbs, 1), 'peak': HBM_PEAK_GBS,
+            'unit': 'GB/s', 'frac': round(hbm_frac, 4)}
+  roof.update({
+      'traffic': pmc_traffic(dom) if algo == 'dqn' else None,
+      'kernel': PHASE_KERNEL.get(dom, dom) + ' (' + dom + ')',
+      'kernel_ms': round(dom_ms, 5),
+      'algorithmic_flop_per_launch': flops[dom],
+      'algorithmic_bytes_per_launch': nbytes[dom],
+      'mfma_frac': round(mfma_frac, 4), 'hbm_frac': round(hbm_frac, 4),
+      'flop_basis': 'algorithmic f32-equivalent FLOP over the exact-f32 MFMA '
+                    'peak; conv1 fwd / dW issue three bf16 piece products per '
+                    'multiply on bf16 MFMA, counted once here'})
+  return roof
+
+
 def run_gpu(args, g, rem):
   from dqn_mgsc_zoo_amd import replicas as replicas_lib  # pylint: disable=g-import-not-at-top
   json_out = _json_stdout()
@@ -826,6 +915,10 @@ def run_gpu(args, g, rem):
   elapsed_max = reps.max_over_ranks(elapsed, device=dev)
   status_max = reps.max_over_ranks(float(status), device=dev)
   lrn.fetch_outputs()
+  if args.dump_outputs and rank == 0:
+    # the last timed step's outputs, before anything below launches again
+    dump_outputs(args.dump_outputs, learner_outputs(
+        lrn, {'slots': slots, 'weights': wl.weights}))
   per_rank = reps.gather_stats([steps / elapsed, elapsed, float(steps),
                                 float(lrn.loss[0].item())], device=dev)
   # which device each rank ran on, and its replay fill time: a line from N
@@ -840,13 +933,15 @@ def run_gpu(args, g, rem):
     reps.close()
     return 4
 
-  # Per-phase device time (HIP events on the launch stream) for the roofline.
-  phases = lrn.profile(store, slots, weights=wl.weights, iters=args.profile_iters)
-  if 'conv1_fwd' in phases and 'conv2_fwd' not in phases:  # the one conv1..conv3 launch
-    phases = {('conv_fwd' if k == 'conv1_fwd' else k): v for k, v in phases.items()}
-  sampler_ms = wl.time_samplers(args.profile_iters)
-  meta_ms = wl.time_meta(max(20, args.profile_iters // 10))
-  mgsc_learn = wl.time_mgsc_learn()
+  phases, sampler_ms, meta_ms, mgsc_learn = {}, {}, {}, {}
+  if args.full:
+    # Per-phase device time (HIP events on the launch stream) for the roofline.
+    phases = lrn.profile(store, slots, weights=wl.weights, iters=args.profile_iters)
+    if 'conv1_fwd' in phases and 'conv2_fwd' not in phases:  # the one conv1..conv3 launch
+      phases = {('conv_fwd' if k == 'conv1_fwd' else k): v for k, v in phases.items()}
+    sampler_ms = wl.time_samplers(args.profile_iters)
+    meta_ms = wl.time_meta(max(20, args.profile_iters // 10))
+    mgsc_learn = wl.time_mgsc_learn()
   q_tm1, td, loss = lrn.fetch_outputs()
   torch.cuda.synchronize(dev)
   finite = bool(torch.isfinite(lrn.online).all().item())
@@ -857,38 +952,7 @@ def run_gpu(args, g, rem):
     return 0 if (status == 0 and status_after == 0) else 3
 
   value = world * steps / elapsed_max
-  flops = phase_flops(algo, BATCH)
-  nbytes = phase_bytes(algo, BATCH)
-  timed_phases = dict(phases)
-  for k, v in sampler_ms.items():
-    if k in wl.sampler_bytes:  # HBM-bound samplers compete for the roofline
-      timed_phases[k] = v
-      flops[k] = 0
-      nbytes[k] = wl.sampler_bytes[k]
-  dom = max(timed_phases, key=timed_phases.get)
-  dom_ms = timed_phases[dom]
-  # The bound is whichever roof the kernel sits closer to.
-  tflops = flops[dom] / (dom_ms * 1e-3) / 1e12
-  gbs = nbytes[dom] / (dom_ms * 1e-3) / 1e9
-  mfma_frac = tflops / F32_MFMA_PEAK_TFLOPS
-  hbm_frac = gbs / HBM_PEAK_GBS
-  if mfma_frac >= hbm_frac:
-    roof = {'bound': 'mfma', 'achieved': round(tflops, 3),
-            'peak': F32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-            'frac': round(mfma_frac, 4)}
-  else:
-    roof = {'bound': 'hbm', 'achieved': round(gbs, 1), 'peak': HBM_PEAK_GBS,
-            'unit': 'GB/s', 'frac': round(hbm_frac, 4)}
-  roof.update({
-      'traffic': pmc_traffic(dom) if algo == 'dqn' else None,
-      'kernel': PHASE_KERNEL.get(dom, dom) + ' (' + dom + ')',
-      'kernel_ms': round(dom_ms, 5),
-      'algorithmic_flop_per_launch': flops[dom],
-      'algorithmic_bytes_per_launch': nbytes[dom],
-      'mfma_frac': round(mfma_frac, 4), 'hbm_frac': round(hbm_frac, 4),
-      'flop_basis': 'algorithmic f32-equivalent FLOP over the exact-f32 MFMA '
-                    'peak; conv1 fwd / dW issue three bf16 piece products per '
-                    'multiply on bf16 MFMA, counted once here'})
+  roof = dominant_phase_roofline(algo, wl, phases, sampler_ms) if args.full else None
   per_gpu = steps / elapsed
   step_tflops = STEP_FLOP[algo] * per_gpu / 1e12
   step_gbs = STEP_BYTES[algo] * per_gpu / 1e9
@@ -949,7 +1013,10 @@ def run_gpu(args, g, rem):
       'last_loss': float(loss.item()),
       'params_finite': finite,
   }
-  if algo == 'mgsc':
+  out['full'] = bool(args.full)
+  if not args.full:  # not measured in a plain run: absent, not empty
+    del out['phase_ms'], out['sampler_us']
+  if algo == 'mgsc' and args.full:
     # the reference's own per-call timings of this agent (V100 + JAX):
     # dqn_mgsc_batched/run_atari.py:308-315
     out['reference_per_call_ms'] = {'update': 12.24, 'replay_sample_batch': 57.1,
@@ -971,7 +1038,7 @@ def run_gpu(args, g, rem):
     # then the learned-logit draw and the DQN step, in one captured graph;
     # `value` above stays the learner part alone
     out['mgsc_learn_step'] = mgsc_learn
-  if world == 1 and args.cpu_seconds > 0:
+  if args.full and world == 1 and args.cpu_seconds > 0:
     out['cpu_baseline'] = cpu_baseline(args.cpu_seconds, algo)
   else:
     out['cpu_baseline'] = None
@@ -1073,6 +1140,8 @@ def run_agent(args):
   torch.cuda.synchronize(dev)
   elapsed = time.perf_counter() - t0
   _barrier(reps)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, learner_outputs(agent.learner))
   status = agent.check_learner_health()
   ok, msg = replay.check_valid()
   elapsed_max = reps.max_over_ranks(elapsed, device=dev)

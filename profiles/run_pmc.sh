@@ -13,6 +13,6 @@ for SET in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
            "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $SET --output-format csv -d "$OUT/p$i" -o run -- \
-    python3 "$ROOT/bench.py" --steps 200 --warmup 20 --graph 0 --cpu-seconds 0 --profile-iters 2 \
+    python3 "$ROOT/bench.py" --full --steps 200 --warmup 20 --graph 0 --cpu-seconds 0 --profile-iters 2 \
     > "$OUT/p$i.json" 2> "$OUT/p$i.err"
 done

@@ -128,6 +128,50 @@ def test_gpus1_forms_a_process_group():
   assert out['rccl']['last_in_loop_gather']['steps_done'] == [10]
 
 
+def test_dump_outputs_files_and_fixed_sample(tmp_path, monkeypatch):
+  """dump_outputs: one .npy per name, float64 kept and the rest float32; an
+  array above its share of the byte limit is the same seeded sample on
+  every call."""
+  import numpy as np  # pylint: disable=g-import-not-at-top
+  import torch  # pylint: disable=g-import-not-at-top
+  monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 3 * 400)
+  arrays = {'small': torch.arange(6, dtype=torch.int32).reshape(2, 3),
+            'wide': np.arange(50, dtype=np.float64),
+            'big': np.arange(1000, dtype=np.float32)}
+  for d in ('a', 'b'):
+    bench.dump_outputs(str(tmp_path / d), arrays)
+  got = {n: np.load(tmp_path / 'a' / (n + '.npy')) for n in arrays}
+  assert sorted(p.name for p in (tmp_path / 'a').iterdir()) == [
+      'big.npy', 'small.npy', 'wide.npy']
+  assert got['small'].dtype == np.float32 and got['small'].shape == (2, 3)
+  assert got['wide'].dtype == np.float64 and got['wide'].shape == (50,)
+  # 400 bytes each: 100 of big's 1000 float32, in index order, no repeats
+  assert got['big'].dtype == np.float32 and got['big'].shape == (100,)
+  assert np.all(np.diff(got['big']) > 0)
+  assert sum(a.nbytes for a in got.values()) <= 3 * 400
+  for n in arrays:
+    assert np.array_equal(got[n], np.load(tmp_path / 'b' / (n + '.npy')))
+
+
+def test_full_and_dump_outputs_options(tmp_path):
+  """--full and --dump-outputs DIR are accepted; the stand-in step's state
+  after exactly K + W steps lands in DIR/x.npy as float32."""
+  import numpy as np  # pylint: disable=g-import-not-at-top
+  import torch  # pylint: disable=g-import-not-at-top
+  out_dir = tmp_path / 'dump'
+  p = _run_bench(['--gpus', '1', '--steps', '7', '--warmup', '2', '--full',
+                  '--dump-outputs', str(out_dir), '--selftest-cpu'])
+  assert p.returncode == 0, p.stderr[-2000:]
+  line = _json_line(p)
+  assert line['steps'] == 7 and line['ms_per_step'] > 0
+  x = torch.ones((64, 64))
+  for _ in range(9):
+    x = torch.tanh(x @ x / 64.0)
+  got = np.load(out_dir / 'x.npy')
+  assert got.dtype == np.float32 and got.shape == (64, 64)
+  np.testing.assert_allclose(got, x.numpy(), rtol=1e-6)
+
+
 def test_lead_eager_steps_keep_the_timed_count():
   """--lead-eager L: L eager steps, then graphs over the other K - L."""
   p = _run_bench(['--gpus', '1', '--steps', '20', '--warmup', '0',

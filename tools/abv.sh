@@ -8,7 +8,7 @@ mkdir -p gpurun_out/abv
 for r in $(seq 1 $R); do
   for L in "$@"; do
     n=$(basename $L .so)
-    DQZ_LIB=$PWD/$L timeout -k 10 120 python bench.py --steps 20000 --warmup 500 --cpu-seconds 0 \
+    DQZ_LIB=$PWD/$L timeout -k 10 120 python bench.py --full --steps 20000 --warmup 500 --cpu-seconds 0 \
       > gpurun_out/abv/${n}_$r.json 2> gpurun_out/abv/${n}_$r.err
     python -c "import json,sys; d=json.load(open('gpurun_out/abv/${n}_$r.json')); print('$n', $r, d['value'], d['handoff_status'], {k: round(v*1e3,2) for k,v in d['phase_ms'].items()})"
   done

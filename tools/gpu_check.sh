@@ -12,5 +12,5 @@ if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 set -e
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 timeout -k 10 200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver.err
-timeout -k 10 300 python bench.py --cpu-seconds 0 > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 300 python bench.py --full --cpu-seconds 0 > $OUT/bench_default.json 2> $OUT/bench_default.err
 exit $rc

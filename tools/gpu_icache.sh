@@ -11,7 +11,7 @@ mkdir -p $OUT
 export DQZ_ALLOW_STALE=1
 cd /tmp && export TMPDIR=/tmp
 for v in base "$@"; do
-  DQZ_LIB=$ROOT/dqn_mgsc_zoo_amd/libdqz_$v.so timeout -s KILL 240 rocprofv3 --pmc SQC_ICACHE_MISSES SQC_ICACHE_HITS --output-format csv -d $OUT/pmc_$v -o run -- python3 $ROOT/bench.py --steps 1000 --warmup 100 --cpu-seconds 0 --capacity 200000 > $OUT/bench_$v.json 2> $OUT/bench_$v.err
+  DQZ_LIB=$ROOT/dqn_mgsc_zoo_amd/libdqz_$v.so timeout -s KILL 240 rocprofv3 --pmc SQC_ICACHE_MISSES SQC_ICACHE_HITS --output-format csv -d $OUT/pmc_$v -o run -- python3 $ROOT/bench.py --full --steps 1000 --warmup 100 --cpu-seconds 0 --capacity 200000 > $OUT/bench_$v.json 2> $OUT/bench_$v.err
   echo "== $v" >> $OUT/summary.txt
   python3 - $OUT/pmc_$v/run_counter_collection.csv >> $OUT/summary.txt <<'PY'
 import csv, collections, sys

@@ -12,7 +12,7 @@ done
 for r in 1 2; do
   for v in "$@"; do
     if [ "$v" = 0 ]; then L=dqn_mgsc_zoo_amd/libdqz.so; else L=dqn_mgsc_zoo_amd/libdqz_s$v.so; fi
-    DQZ_LIB=$PWD/$L timeout -k 10 120 python bench.py --steps 20000 --warmup 500 --cpu-seconds 0 > $OUT/bench_${v}_$r.json 2> $OUT/bench_${v}_$r.err
+    DQZ_LIB=$PWD/$L timeout -k 10 120 python bench.py --full --steps 20000 --warmup 500 --cpu-seconds 0 > $OUT/bench_${v}_$r.json 2> $OUT/bench_${v}_$r.err
     python -c "import json; d=json.load(open('$OUT/bench_${v}_$r.json')); print('$v', $r, d['value'], {k: round(x*1e3,2) for k,x in d['phase_ms'].items()})" | tee -a $OUT/summary.txt
   done
 done

@@ -20,11 +20,11 @@ set -e
 for r in $(seq 1 $R); do
   for L in "$@"; do
     n=$(basename $L .so)
-    DQZ_ALLOW_STALE=1 DQZ_LIB=$PWD/$L timeout -k 10 120 python bench.py --steps ${STEPS:-20000} --warmup 500 --cpu-seconds 0 \
+    DQZ_ALLOW_STALE=1 DQZ_LIB=$PWD/$L timeout -k 10 120 python bench.py --full --steps ${STEPS:-20000} --warmup 500 --cpu-seconds 0 \
       > $OUT/${n}_$r.json 2> $OUT/${n}_$r.err
     python -c "import json; d=json.load(open('$OUT/${n}_$r.json')); print('$n', $r, d['value'], d['handoff_status'], {k: round(v*1e3,2) for k,v in d['phase_ms'].items()})" | tee -a $OUT/summary.txt
   done
 done
 timeout -k 10 200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver.err
-timeout -k 10 300 python bench.py --cpu-seconds 0 > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 300 python bench.py --full --cpu-seconds 0 > $OUT/bench_default.json 2> $OUT/bench_default.err
 exit $rc

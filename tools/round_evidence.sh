@@ -16,9 +16,9 @@ if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 set -e
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 timeout -k 10 200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver.err
-timeout -k 10 300 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-timeout -k 10 300 python bench.py --algo per --cpu-seconds 0 > $OUT/bench_per.json 2> $OUT/bench_per.err
-timeout -k 10 300 python bench.py --algo mgsc --cpu-seconds 0 > $OUT/bench_mgsc.json 2> $OUT/bench_mgsc.err
+timeout -k 10 300 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 300 python bench.py --full --algo per --cpu-seconds 0 > $OUT/bench_per.json 2> $OUT/bench_per.err
+timeout -k 10 300 python bench.py --full --algo mgsc --cpu-seconds 0 > $OUT/bench_mgsc.json 2> $OUT/bench_mgsc.err
 timeout -k 10 300 python bench.py --algo agent --steps 2000 --warmup 50 > $OUT/bench_agent.json 2> $OUT/bench_agent.err
 bash tools/bench_median.sh $OUT/median > $OUT/bench_median5.json
 timeout -k 10 300 python tools/meta_bench.py --steps 100 > $OUT/meta_bench.json 2> $OUT/meta_bench.err
