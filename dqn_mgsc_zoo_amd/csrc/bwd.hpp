@@ -1,13 +1,5 @@
 // bwd.hpp — backward kernels specialised for the NatureQNetwork at small B.
 #pragma once
-// Timing-only probes (numerics wrong by design): DQZ_EXP_DXFAST / _DWFAST
-// run a third of the conv3 / conv2 dX (dW) MFMA K steps.
-#ifndef DQZ_EXP_DXFAST
-#define DQZ_EXP_DXFAST 0
-#endif
-#ifndef DQZ_EXP_DWFAST
-#define DQZ_EXP_DWFAST 0
-#endif
 #include "common.hpp"
 #include "conv1.hpp"
 #include "fwd.hpp"
@@ -228,7 +220,7 @@ __device__ __forceinline__ void conv3_bwd_dx(const Conv3BwdArgs& a, float* s_win
 #pragma unroll
   for (int m = 0; m < 3; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int kk = 0; kk < 36; ++kk) if (!DQZ_EXP_DXFAST || kk % 3 == 0) {
+  for (int kk = 0; kk < 36; ++kk) {
     const int tp = kk >> 2;  // tap' = kh'*3 + kw'
     const int off = (tp / 3) * C3X_RS + (tp % 3) * C3X_S + 4 * (kk & 3);
 #pragma unroll
@@ -263,9 +255,8 @@ __device__ __forceinline__ void conv3_bwd_dx(const Conv3BwdArgs& a, float* s_win
   if constexpr (PUB) a.sync.arrive(b);
 }
 
-// conv3 dW job (sample b, output-channel quarter nq).  (Round 3 measured
-// jobs that accumulate several samples, and a per-XCD pre-reduction of the
-// per-sample slabs inside the launch: both slower, commit 1a3be58.)
+// conv3 dW job (sample b, output-channel quarter nq).
+// alternatives measured: DESIGN §4 "Tried in round 3"
 __device__ __forceinline__ void conv3_bwd_dw(const Conv3BwdArgs& a, float* s_win, int b, int nq) {
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int n = lane & 15, kq = lane >> 4;
@@ -309,7 +300,7 @@ __device__ __forceinline__ void conv3_bwd_dw(const Conv3BwdArgs& a, float* s_win
   // float4 (the products and their k order are those of the transposed form,
   // so the values are the same bits)
 #pragma unroll
-  for (int kk = 0; kk < 13; ++kk) if (!DQZ_EXP_DWFAST || kk % 3 == 0)
+  for (int kk = 0; kk < 13; ++kk)
 #pragma unroll
     for (int tp = 0; tp < 9; ++tp) {
       const int off = (tp / 3) * C3W_RS + (tp % 3) * C3W_S;
@@ -429,7 +420,7 @@ __device__ __forceinline__ void conv2_bwd_dx(const Conv2BwdArgs& a, float* s_win
   for (int m = 0; m < MT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
   float last[4] = {0.f, 0.f, 0.f, 0.f};  // pixels 96..99 (a = 9, c = 6..9), this lane's k rows
 #pragma unroll
-  for (int kk = 0; kk < 16; ++kk) if (!DQZ_EXP_DXFAST || kk % 3 == 0) {
+  for (int kk = 0; kk < 16; ++kk) {
     const int tp = kk >> 2;  // (u', v') = (tp >> 1, tp & 1)
     const int off = (tp >> 1) * C2X_RS + (tp & 1) * C2X_S + 4 * (kk & 3);
 #pragma unroll
@@ -548,7 +539,7 @@ __device__ __forceinline__ void conv2_bwd_dw_split(const Conv2BwdArgs& a, float*
   // A = dy2 (rows: co), B = y1 (columns: ci): a lane's accumulators are four
   // consecutive co, stored as one float4 (same bits as the transposed form)
 #pragma unroll
-  for (int kk = 0; kk < 21; ++kk) if (!DQZ_EXP_DWFAST || kk % 3 == 0)
+  for (int kk = 0; kk < 21; ++kk)
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
       const float av = s_win[pb[kk] + 16 * mt];
@@ -772,9 +763,7 @@ __device__ __forceinline__ void fc1_dx_block(const Fc1BwdArgs& a, float* smem, i
 // halves of 16 rows), loaded before the head, and forms dy3 = relu'(y3)
 // (W1 dz1) as VALU dot products (a one-row GEMV: 16 lanes per row, 32
 // columns per lane in column order, then a 16-lane sum); it also writes its
-// share of the dX-ordered W3 / W2 copies, as fc1_dx_kernel does.  (Round 5's
-// first form ran the head in block 0 and handed dz1 to the other blocks
-// in-launch: 9.0 us; the head's round trips and the hand-off were serial.)
+// share of the dX-ordered W3 / W2 copies, as fc1_dx_kernel does.
 constexpr int FC1X1_ROWS = 32;
 constexpr int FC1X1_BLOCKS = FLAT / FC1X1_ROWS;  // 98
 
@@ -864,37 +853,13 @@ DQZ_STEP_KERNEL __launch_bounds__(256) void fc1_dx_kernel(Fc1BwdArgs a) {
 // leading workgroups: wave 0 of the first runs per_write_back_wave beside the
 // whole backward (the TD errors are final since the head), the other seven
 // exit at once (the sample ranges keep their XCD alignment).
-// Timing-only experiment switches (never set in a product build; the
-// numerics of a build with them are wrong): DQZ_EXP_SKIP bit 0 skips the fc1
-// dW range, bit 1 conv3 dW, bit 2 conv2 dW, bit 3 conv1 dW (skipped
-// consumers still pass their hand-off waits, so the words stay balanced).
-#ifndef DQZ_EXP_SKIP
-#define DQZ_EXP_SKIP 0
-#endif
-// (Round 5: the optimizer update as this launch's last range, each update
-// block waiting for the dW jobs of its layers, which stored their slabs
-// write-through and drained before arriving: correct, but the drains
-// stretched the conv1 dW tail by 3 us, as much as the update launch's
-// boundary saved (16,210 against 16,244 steps/s; first-order meta-update
-// 193 -> 201 us; profiles/r05/s13).  With a thousand update blocks polling
-// three shared words the launch ran 1.3x slower (s10-s12).  Removed.)
 // Wave issue priority (s_setprio): the conv3 / conv2 dX waves 3, the conv1
 // dW waves (the launch's tail, behind dy1) 2, every other dW wave the default
 // 0, so on a SIMD shared with dW waves the chain's instructions issue first
 // (round 6: +0.1 / +0.4 / +1.1 % in three interleaved A/B sessions; conv2 /
 // conv3 dW at 1 as well: +0.3 %; the forward's conv2 / conv3 consumers above
 // their producers: -0.8 %; profiles/r06/prio).
-// (Round 6, also measured and not kept: the fc1 RMSProp outputs and the conv
-// dW slabs as write-through sc1 stores, so the backward leaves 32 MB fewer
-// dirty lines for the boundary before the update: -0.8 %, r06/prio; the
-// XCD's dirty lines written back early instead, by an agent-scope release
-// fence in the last 8 / 32 fc1 dW blocks: -1.9 / -6.6 %, r06/wbl2.)
-// (Round 5, also removed: the dX chain on XCDs 0..L-1 and the dW sets on the
-// other XCDs.  With L = 4 the chain ended 0.5 us sooner, but the dW side
-// became the tail (+2.8 us) and the boundary after the launch grew 2.8 ->
-// 5.8 us, the written lines now dirty in half the L2s: 15,873-15,901
-// against 16,137-16,223 steps/s; L = 3 / 5 / 6 15,210 / 14,750 / 13,200;
-// profiles/r05/split.)
+// alternatives measured: DESIGN §4 "Tried in round 5", "Round 6: what was tried on the step"
 template <bool WB>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void bwd_bc_kernel(
     Conv3BwdArgs c3, Fc1BwdArgs f1, Conv2BwdArgs c2, Conv1DwArgs c1, PerWbArgs wb) {
@@ -926,7 +891,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   }
   i -= 8 * B8;
   if (i < NF) {
-    if (DQZ_EXP_SKIP & 1) return;
     fc1_dw_body(f1, smem, i);
     return;
   }
@@ -944,7 +908,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   if (i < 4 * B8) {
     const SampleJob sj = xcd_sample_job_at(i, 4, c3.B);
     if (!sj.valid) return;
-    if (DQZ_EXP_SKIP & 2) return;
     DQZ_STAMP(12, 0);
     conv3_bwd_dw(c3, smem, sj.s, sj.job);
     DQZ_STAMP(12, 3);
@@ -957,10 +920,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   if (i < 8 * B8) {
     const SampleJob sj = xcd_sample_job_at(i, 8, c1.B);
     if (!sj.valid) return;
-    if (DQZ_EXP_SKIP & 8) {
-      c1.sync1.wait(sj.s);
-      return;
-    }
     __builtin_amdgcn_s_setprio(2);  // the launch's tail next
     conv1_dw_half(c1, smem, sj.job >> 1, sj.job & 1, sj.s);
     return;
@@ -968,10 +927,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   i -= 8 * B8;
   const SampleJob sj = xcd_sample_job_at(i, 8, c2.B);
   if (!sj.valid) return;
-  if (DQZ_EXP_SKIP & 4) {
-    c2.sync.wait(sj.s);
-    return;
-  }
   DQZ_STAMP(13, 0);
   conv2_bwd_dw_split(c2, smem, sj.s, sj.job >> 1, sj.job & 1);
   DQZ_STAMP(13, 3);

@@ -34,16 +34,6 @@
 #pragma once
 #include "common.hpp"
 
-// Timing-only builds (tools/gpu_hvp_split.sh): DQZ_EXP_HVP_SKIP is a mask of
-// block ranges that return at once (1 t12, 2 b3, 4 b1's sums — its arrival
-// stays, 8 conv2 / conv3 parameter rows, 16 fc1 parameters, 32 conv1
-// parameter rows, 64 t34, 128 b2).  The numerics of those builds are wrong
-// by design.
-#ifndef DQZ_EXP_HVP_SKIP
-#define DQZ_EXP_HVP_SKIP 0
-#endif
-
-
 namespace dqz {
 
 struct HvpArgs {
@@ -153,7 +143,6 @@ struct HvpT12Smem {
 // (a form with 130 scalar loads per thread waited for its loads in two
 // rounds: a wave cannot hold more than 63 in flight).
 __device__ __forceinline__ void hvp_t12_block(const HvpArgs& a, int i, HvpT12Smem& s) {
-  if (DQZ_EXP_HVP_SKIP & 1) return;
   const int t = threadIdx.x, p = i >> 2, g = i & 3;
   const int oh = p / C2O, ow = p % C2O;
   const int kh = t >> 5, co = t & 31;
@@ -304,7 +293,6 @@ __device__ __forceinline__ void hvp_s1_block(const HvpArgs& a, float* s_w) {
 // stages all of Wdot2 (512 x A) in LDS beside the row loads, so a's load
 // runs under them instead of before another trip (the gathers of column a).
 __device__ __forceinline__ void hvp_b3_block(const HvpArgs& a, int i, float* s_w2) {
-  if (DQZ_EXP_HVP_SKIP & 2) return;
   constexpr int R = 4;
   const int t = threadIdx.x, lane = t & 63, k0 = 16 * i + R * (t >> 6);
   const int act = __float_as_int(a.rec[0].x);
@@ -391,7 +379,6 @@ struct HvpT34Smem {
   float ty[16];
 };
 __device__ __forceinline__ void hvp_t34_block(const HvpArgs& a, int i, HvpT34Smem& s) {
-  if (DQZ_EXP_HVP_SKIP & 64) return;
   const int t = threadIdx.x, p = i >> 2, g = i & 3;
   const int rh = t >> 7, cq = t & 127;
   float4 fw[8], fwd[8], fy[2];
@@ -460,7 +447,6 @@ __device__ __forceinline__ void hvp_t34_block(const HvpArgs& a, int i, HvpT34Sme
 // transposed conv3, stride 1).  Block (pix, 16-channel group g); thread
 // (ci, output-channel quad cs = t % 16): 16-byte W loads along co.
 __device__ __forceinline__ void hvp_b2_block(const HvpArgs& a, int i, float (*s_r)[17]) {
-  if (DQZ_EXP_HVP_SKIP & 128) return;
   const int t = threadIdx.x, pix = i >> 2, g = i & 3;
   const int ih = pix / C2O, iw = pix % C2O, cs = t & 15, cl = t >> 4, ci = 16 * g + cl;
   // the nine taps' operands loaded together (taps outside the output are
@@ -514,10 +500,6 @@ __global__ __launch_bounds__(256) void hvp_l2_kernel(HvpArgs a) {
 // transposed conv2, stride 2: at most 2 x 2 live taps).  Block pix; thread
 // (ci = t / 8, output-channel octet cs = t % 8).
 __device__ __forceinline__ void hvp_b1_block(const HvpArgs& a, int pix, float (*s_r)[9]) {
-  if (DQZ_EXP_HVP_SKIP & 4) {
-    a.td1_pub.arrive(0);
-    return;
-  }
   const int t = threadIdx.x;
   const int ih = pix / C1O, iw = pix % C1O, cs = t & 7, ci = t >> 3;
   // the 2 x 2 taps of this pixel's stride phase, every operand loaded before
@@ -578,7 +560,6 @@ template <int IH, int CI, int K, int S, int CO, int OH>
 __device__ __forceinline__ void hvp_g_conv_row(const HvpArgs& a, const float* y, const float* yd, const float* d,
                                                const float* dd, int k, int64_t off_w, int64_t off_b, float (*s_r)[64],
                                                const HqOut& ho) {
-  if (DQZ_EXP_HVP_SKIP & 8) return;
   const int t = threadIdx.x, co = t & 63, sp = t >> 6;  // 4 position splits
   constexpr int P = OH * OH, PS = (P + 3) / 4;
   const int p0 = sp * PS;
@@ -657,7 +638,6 @@ __device__ __forceinline__ void hvp_g_hidden(const HvpArgs& a, int i, float (*s_
 // ((4 i + u) 256 + t) 4), every group's loads before the first store.
 constexpr int HVP_G_FCU = 4;
 __device__ __forceinline__ void hvp_g_fc1(const HvpArgs& a, int i, const HqOut& ho) {
-  if (DQZ_EXP_HVP_SKIP & 16) return;
   const int t = threadIdx.x;
   constexpr int U = HVP_G_FCU;
   int64_t e[U];
@@ -696,7 +676,6 @@ __device__ __forceinline__ void hvp_g_fc1(const HvpArgs& a, int i, const HqOut& 
 // scattered byte loads per thread was 11 of the gradient launch's 20 us in
 // round 4), ddot1 is read with sc1 loads after it.
 __device__ __forceinline__ void hvp_g_conv1(const HvpArgs& a, int k, float (*s_r)[64], float* s_x, const HqOut& ho) {
-  if (DQZ_EXP_HVP_SKIP & 32) return;
   const int t = threadIdx.x, co = t & 31, sp = t >> 5;
   if (k < C1KK) {
     const int kh = k / (C1K * FC), kw = (k / FC) % C1K, ci = k % FC;

@@ -127,12 +127,9 @@ int dqz_learner_destroy(dqz_learner* L) {
 
 // conv1..fc1 forward of Z network copies (phases 0-3): conv1 -> conv2 ->
 // conv3 as one hand-off launch (fwd_conv_kernel; since conv1 runs on bf16
-// MFMA: 15,590 -> 16,050 steps/s against three launches, which round 4
-// removed), then the split-K fc1.  Used by the learner step and the actor.
-// (Round 5: fc1 inside the forward launch for launches of at most 16
-// samples, its W1 loads issued at dispatch and y3 handed over per sample,
-// measured slower at B = 1: the W1 stream stretched the conv chain by 0.9-1.6
-// us, profiles/r05/s8, s9; removed.)
+// MFMA: 15,590 -> 16,050 steps/s against three launches), then the split-K
+// fc1.  Used by the learner step and the actor.
+// alternatives measured: DESIGN §4 "Tried in round 5"
 static int forward_impl(dqz_learner* L, const NetZ& nz, int Z, int B, const Conv1Src& src, hipStream_t st,
                         PhaseEvents pe) {
   Conv1FwdArgs c1{};

@@ -1,7 +1,7 @@
 #!/bin/bash
-# Code-layout sweep: one 20,000-step default bench per prebuilt library
-# (libdqz_<name>.so; e.g. DQZ_LAYOUT_PAD variants from tools/build_variants.sh),
-# base first and last.  A/B arms only (DQZ_ALLOW_STALE for the variants).
+# Variant sweep: one 20,000-step default bench per prebuilt library
+# (libdqz_<name>.so, e.g. from tools/build_variants.sh), base first and
+# last.  A/B arms only (DQZ_ALLOW_STALE for the variants).
 # usage: bash tools/gpu_layout_sweep.sh TAG variant...
 set -eo pipefail
 ROOT=$(pwd)

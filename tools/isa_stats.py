@@ -1,18 +1,14 @@
-"""Per-kernel ISA counters of libdqz (integer-division expansions, float
-divisions, vmcnt(0) drains, loads, MFMAs).  usage: python tools/isa_stats.py"""
-import os
+"""Per-kernel ISA counters of libdqz's two code objects (integer-division
+expansions, float divisions, vmcnt(0) drains, loads, MFMAs).
+usage: python tools/isa_stats.py [substring of the kernel's name]"""
 import re
 import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = os.path.join(tempfile.gettempdir(), 'dqz_isa.s')
-subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only', '-S',
-                       '-I' + os.path.join(ROOT, 'include'), '-o', out,
-                       os.path.join(ROOT, 'dqn_mgsc_zoo_amd', 'csrc', 'learner.hip')], stderr=subprocess.DEVNULL)
+import device_code
+
 stats, cur = {}, None
-for line in open(out):
+for line in device_code.asm_lines():
   m = re.match(r'^(_Z\w+):', line)
   if m:
     cur = m.group(1)

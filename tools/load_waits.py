@@ -1,22 +1,15 @@
 """Flags kernels whose loads before the first barrier are split by vmcnt
 waits (a load issued after a wait costs an extra memory round trip).
-usage: python tools/load_waits.py [asm.s]   (builds the device asm if omitted)"""
-import os
+usage: python tools/load_waits.py [asm.s]   (builds both units' device asm if omitted)"""
 import re
 import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if len(sys.argv) > 1:
-  path = sys.argv[1]
-else:
-  path = os.path.join(tempfile.gettempdir(), 'dqz_waits.s')
-  subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '--cuda-device-only',
-                         '-S', '-I' + os.path.join(ROOT, 'include'), '-o', path,
-                         os.path.join(ROOT, 'dqn_mgsc_zoo_amd', 'csrc', 'learner.hip')], stderr=subprocess.DEVNULL)
+import device_code
+
+lines = open(sys.argv[1]) if len(sys.argv) > 1 else device_code.asm_lines()
 cur, seen_barrier, waited, late = None, False, False, {}
-for line in open(path):
+for line in lines:
   m = re.match(r'^(_Z\w+):', line)
   if m:
     cur, seen_barrier, waited = m.group(1), False, False
