@@ -610,6 +610,27 @@ int dqz_target_copy(float* target, const float* online, int64_t total, void* str
   return DQZ_OK;
 }
 
+int dqz_learner_debug_activations(dqz_learner* L, int z, float* y1, float* y2, float* y3, float* h1, float* q,
+                                  float* dz1, float* dy3, float* dy2, float* dy1, void* stream) {
+  if (!L) return fail(DQZ_ERR_INVALID, "null learner");
+  if (z < 0 || z >= L->Z) return fail(DQZ_ERR_INVALID, "z must be in [0, %d)", L->Z);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t B = L->cfg.batch, A = L->cfg.num_actions;
+  // slab zc of a [Z][B][n] forward array, or the one [B][n] backward array
+  const struct {
+    float* dst;
+    const float* src;
+    int64_t n, zc;
+  } rows[] = {{y1, L->y1, (int64_t)C1M * C1CO, z}, {y2, L->y2, (int64_t)C2M * C2CO, z}, {y3, L->y3, FLAT, z},
+              {h1, L->h1, HID, z},                 {q, L->q, A, z},                     {dz1, L->dz1, HID, 0},
+              {dy3, L->dy3, FLAT, 0},              {dy2, L->dy2, (int64_t)C2M * C2CO, 0},
+              {dy1, L->dy1, (int64_t)C1M * C1CO, 0}};
+  for (const auto& r : rows)
+    if (r.dst)
+      DQZ_HIP(hipMemcpyAsync(r.dst, r.src + r.zc * B * r.n, sizeof(float) * B * r.n, hipMemcpyDeviceToDevice, st));
+  return DQZ_OK;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------

@@ -215,6 +215,29 @@ class Learner:
     counter (sample >= 0) and cap the bounded spin at `spin_max` polls."""
     _native.check(_native.lib().dqz_learner_debug_stall(self._h, int(sample), int(spin_max)))
 
+  def fetch_activations(self, z=0, backward=False, stream=None):
+    """Diagnostic (dqz_learner_debug_activations): the intermediates of the
+    most recent step / gradient call as a dict of fresh device tensors.
+    Network copy z (0 online(s_tm1), 1 target(s_t), 2 online(s_t)): y1
+    [B,20,20,32], y2 [B,9,9,64], y3 [B,7,7,64], h1 [B,512] (post-ReLU) and q
+    [B,A]; with `backward`, also dz1 [B,512], dy3 [B,7,7,64], dy2 [B,9,9,64]
+    and dy1 [B,20,20,32] of copy 0: d loss / d pre-activation, each already
+    multiplied by its own ReLU mask."""
+    b, a = self.batch_size, self.network.num_actions
+    shapes = dict(y1=(b, 20, 20, 32), y2=(b, 9, 9, 64), y3=(b, 7, 7, 64),
+                  h1=(b, 512), q=(b, a))
+    if backward:
+      shapes.update(dz1=(b, 512), dy3=(b, 7, 7, 64), dy2=(b, 9, 9, 64),
+                    dy1=(b, 20, 20, 32))
+    out = {k: torch.empty(s, dtype=torch.float32, device=self.device)
+           for k, s in shapes.items()}
+    _native.check(_native.lib().dqz_learner_debug_activations(
+        self._h, int(z),
+        *(_native.ptr(out.get(k)) for k in ('y1', 'y2', 'y3', 'h1', 'q', 'dz1',
+                                             'dy3', 'dy2', 'dy1')),
+        _native.stream_handle(stream)))
+    return out
+
   def q_values(self, states, params=None, stream=None):
     """network.apply(params, s).q_values for uint8 [n,84,84,4] device states."""
     params = self.online if params is None else params

@@ -217,6 +217,29 @@ int dqz_learner_sync_status(dqz_learner* learner, int* status);
  * exercised.  Synchronises the device. */
 int dqz_learner_debug_stall(dqz_learner* learner, int sample, unsigned spin_max);
 
+/* Diagnostic (tests): device-to-device copies of the intermediates the
+ * learner's scratch holds after its most recent learner step, gradient call
+ * or forward (any output may be NULL; no kernel is launched; the copies are
+ * ordered on `stream`).  Every array is plain f32, sample-major, NHWC.
+ * Forward, network copy z — 0 online(s_tm1), 1 target(s_t), 2 online(s_t)
+ * (double-Q and PER only); z outside [0, Z) is DQZ_ERR_INVALID:
+ *   y1 [B][20][20][32], y2 [B][9][9][64], y3 [B][7][7][64] (= [B][3136], the
+ *   flatten order of fc1), h1 [B][512]: the post-ReLU activations;
+ *   q [B][A].
+ * Backward, of copy 0 only (the one differentiated pass):
+ *   dz1 [B][512], dy3 [B][3136], dy2 [B][9][9][64], dy1 [B][20][20][32]:
+ *   d loss / d pre-activation of fc1, conv3, conv2, conv1, i.e. each already
+ *   multiplied by its own layer's ReLU mask (y > 0), which is where the
+ *   backward kernels take their masks from.  In a gradient call or a step
+ *   the cotangent at q is -clip(w td / B); the MGSC meta passes weight it
+ *   per sample instead.
+ * After dqz_forward / dqz_forward_slots / dqz_act of n <= B states only
+ * copy 0 is current, packed as [n][...] at the start of each array; q is
+ * written by dqz_act alone (the other two write the caller's q_out), and the
+ * backward arrays keep the last step's values. */
+int dqz_learner_debug_activations(dqz_learner* learner, int z, float* y1, float* y2, float* y3, float* h1,
+                                  float* q, float* dz1, float* dy3, float* dy2, float* dy1, void* stream);
+
 /* Q-values of the NatureQNetwork for uint8 HWC states [n][84][84][4]
  * (network.apply(...).q_values, networks.py:352-363; used by select_action,
  * dqn/agent.py:121-131).  q_out: device f32 [n][A]. n <= learner batch. */

@@ -72,25 +72,45 @@ def head_params(params, shared_bias):
   return w2, b2
 
 
-def forward(params, s, shared_bias=False):
-  """Q-values and intermediates for uint8 states s [B,84,84,4]."""
+def forward(params, s, shared_bias=False, masks=None):
+  """Q-values and intermediates for uint8 states s [B,84,84,4].
+
+  masks: None, or four boolean arrays in the layers' shapes ([B,20,20,32],
+  [B,9,9,64], [B,7,7,64], [B,512]) that replace the ReLU decisions: each
+  activation is z * mask instead of max(z, 0).  Pinning them to another
+  implementation's decisions takes the ReLU kink out of a comparison with it
+  (a pre-activation within f32 rounding of 0 falls on either side).  The
+  masks used, given or not, go into the cache as 'masks'; `backward` and
+  `hvp` read them from there.
+  """
   x = np.asarray(s).astype(np.float32).astype(np.float64) / 255.0
   cache = {'x0': x}
+  used = []
   for i, ((k, st, _, co), name) in enumerate(zip(CONV_SPECS, CONV_NAMES)):
     w = np.asarray(params[name]['w'], np.float64)
     b = np.asarray(params[name]['b'], np.float64)
     cols = _im2col(x, k, st)
     z = cols @ w.reshape(-1, co) + b
-    x = np.maximum(z, 0.0)
+    if masks is None:
+      x = np.maximum(z, 0.0)
+      used.append(x > 0)
+    else:
+      used.append(np.asarray(masks[i], bool).reshape(z.shape))
+      x = z * used[i]
     cache['cols%d' % i] = cols
     cache['y%d' % i] = x
   flat = x.reshape(x.shape[0], -1)
   w1 = np.asarray(params[_HEAD + '/linear']['w'], np.float64)
   b1 = np.asarray(params[_HEAD + '/linear']['b'], np.float64)
-  h1 = np.maximum(flat @ w1 + b1, 0.0)
+  if masks is None:
+    h1 = np.maximum(flat @ w1 + b1, 0.0)
+    used.append(h1 > 0)
+  else:
+    used.append(np.asarray(masks[3], bool).reshape(flat.shape[0], -1))
+    h1 = (flat @ w1 + b1) * used[3]
   w2, b2 = head_params(params, shared_bias)
   q = h1 @ w2 + b2
-  cache.update(flat=flat, h1=h1)
+  cache.update(flat=flat, h1=h1, masks=tuple(used))
   return q, cache
 
 
@@ -123,15 +143,15 @@ def backward(params, cache, dq, shared_bias=False):
     grads[_HEAD] = {'b': np.array([dq.sum()])}
   else:
     grads[_HEAD + '/linear_1']['b'] = dq.sum(axis=0)
-  dh1 = (dq @ w2.T) * (h1 > 0)
+  masks = cache['masks']
+  dh1 = (dq @ w2.T) * masks[3]
   w1 = np.asarray(params[_HEAD + '/linear']['w'], np.float64)
   grads[_HEAD + '/linear'] = {'w': flat.T @ dh1, 'b': dh1.sum(axis=0)}
   dflat = dh1 @ w1.T
   dy = dflat.reshape(cache['y2'].shape)
   for i in (2, 1, 0):
     k, st, _, co = CONV_SPECS[i]
-    y = cache['y%d' % i]
-    dz = dy * (y > 0)
+    dz = dy * masks[i]
     cols = cache['cols%d' % i]
     grads[CONV_NAMES[i]] = {
         'w': (cols.reshape(-1, cols.shape[-1]).T @ dz.reshape(-1, co)).reshape(
@@ -147,21 +167,25 @@ def backward(params, cache, dq, shared_bias=False):
 
 
 def td_loss(q_tm1, a_tm1, r_t, discount_t, q_target_t, q_selector_t=None,
-            weights=None, grad_error_bound=1.0 / 32):
+            weights=None, grad_error_bound=1.0 / 32, select=None):
   """TD errors, mean loss and d loss / d q_tm1.
 
   q_learning: target = r + d * max_a q_target_t; double_q_learning: target =
   r + d * q_target_t[argmax q_selector_t] (first maximum).  loss =
   mean(0.5 td^2 [* w]).  The cotangent at td is clip(w td / B, +-bound)
-  because rlax.clip_gradient sits between td and l2_loss.
+  because rlax.clip_gradient sits between td and l2_loss.  select (int [B]):
+  the selected actions, in place of argmax(q_selector_t) (a near-tie pinned
+  to another implementation's choice); only read when q_selector_t is given.
   """
   b = q_tm1.shape[0]
   idx = np.arange(b)
   a_tm1 = np.asarray(a_tm1, np.int64)
   if q_selector_t is None:
     v = q_target_t.max(axis=1)
-  else:
+  elif select is None:
     v = q_target_t[idx, np.argmax(q_selector_t, axis=1)]
+  else:
+    v = q_target_t[idx, np.asarray(select, np.int64)]
   target = np.asarray(r_t, np.float64) + np.asarray(discount_t, np.float64) * v
   td = target - q_tm1[idx, a_tm1]
   w = np.ones(b) if weights is None else np.asarray(weights, np.float64)
@@ -201,26 +225,33 @@ def adam(params, grads, m, v, count, lr, b1=0.9, b2=0.999, eps=1e-8):
 
 def learner_step(online, target, mu, nu, s_tm1, a_tm1, r_t, discount_t, s_t,
                  algo='dqn', weights=None, lr=2.5e-4, decay=0.95,
-                 eps=0.01 / 32**2, grad_error_bound=1.0 / 32):
+                 eps=0.01 / 32**2, grad_error_bound=1.0 / 32, masks=None,
+                 select=None):
   """One `update` (dqn/agent.py:109-119; prioritized/agent.py:115-127).
 
   algo: 'dqn' (q_learning, per-action bias), 'double' or 'per'
   (double_q_learning, shared-bias head; 'per' weights the loss).
-  Returns dict(q_tm1, td, loss, params, mu, nu, grads).
+  masks: the ReLU decisions of the online(s_tm1) pass (see `forward`; the
+  other passes are not differentiated); select: the double-Q / PER action
+  choice at s_t (see `td_loss`).
+  Returns dict(q_tm1, q_target_t, q_selector_t (None for 'dqn'), td, loss,
+  params, mu, nu, grads, masks (the four used by the online(s_tm1) pass)).
   """
   shared = algo != 'dqn'
-  q_tm1, cache = forward(online, s_tm1, shared)
+  q_tm1, cache = forward(online, s_tm1, shared, masks)
   q_target_t, _ = forward(target, s_t, shared)
   q_sel = None
   if algo != 'dqn':
     q_sel, _ = forward(online, s_t, shared)
   td, loss, dq = td_loss(q_tm1, a_tm1, r_t, discount_t, q_target_t, q_sel,
-                         weights if algo == 'per' else None, grad_error_bound)
+                         weights if algo == 'per' else None, grad_error_bound,
+                         select)
   grads = backward(online, cache, dq, shared)
   new_p, new_mu, new_nu = rmsprop_centered(online, grads, mu, nu, lr, decay,
                                            eps)
-  return dict(q_tm1=q_tm1, q_target_t=q_target_t, td=td, loss=loss,
-              params=new_p, mu=new_mu, nu=new_nu, grads=grads)
+  return dict(q_tm1=q_tm1, q_target_t=q_target_t, q_selector_t=q_sel, td=td,
+              loss=loss, params=new_p, mu=new_mu, nu=new_nu, grads=grads,
+              masks=cache['masks'])
 
 
 def zeros_like_tree(tree):
@@ -274,6 +305,7 @@ def hvp(params, cache, dq, tangent, shared_bias=False):
   def pw(name, leaf='w'):
     return np.asarray(params[name][leaf], np.float64)
 
+  masks = cache['masks']
   # tangent forward
   ydot = [None, None, None]
   colsdot = [None, None, None]
@@ -284,12 +316,12 @@ def hvp(params, cache, dq, tangent, shared_bias=False):
     if prev is not None:
       colsdot[i] = _im2col(prev, k, st)
       zdot = zdot + colsdot[i] @ pw(name).reshape(-1, co)
-    ydot[i] = zdot * (cache['y%d' % i] > 0)
+    ydot[i] = zdot * masks[i]
     prev = ydot[i]
   flat, h1 = cache['flat'], cache['h1']
   flatdot = ydot[2].reshape(flat.shape)
   w1 = pw(_HEAD + '/linear')
-  h1dot = (flat @ tw(_HEAD + '/linear') + flatdot @ w1 + tw(_HEAD + '/linear', 'b')) * (h1 > 0)
+  h1dot = (flat @ tw(_HEAD + '/linear') + flatdot @ w1 + tw(_HEAD + '/linear', 'b')) * masks[3]
   w2, _ = head_params(params, shared_bias)
   w2dot = tw(_HEAD + '/linear_1')
   out = {}
@@ -298,8 +330,8 @@ def hvp(params, cache, dq, tangent, shared_bias=False):
     out[_HEAD] = {'b': np.zeros(1)}
   else:
     out[_HEAD + '/linear_1']['b'] = np.zeros(dq.shape[1])
-  dh1 = (dq @ w2.T) * (h1 > 0)
-  dh1dot = (dq @ w2dot.T) * (h1 > 0)
+  dh1 = (dq @ w2.T) * masks[3]
+  dh1dot = (dq @ w2dot.T) * masks[3]
   out[_HEAD + '/linear'] = {'w': flatdot.T @ dh1 + flat.T @ dh1dot,
                             'b': dh1dot.sum(axis=0)}
   dflat = dh1 @ w1.T
@@ -308,7 +340,7 @@ def hvp(params, cache, dq, tangent, shared_bias=False):
   dydot = dflatdot.reshape(cache['y2'].shape)
   for i in (2, 1, 0):
     k, st, _, co = CONV_SPECS[i]
-    mask = cache['y%d' % i] > 0
+    mask = masks[i]
     dz, dzdot = dy * mask, dydot * mask
     cols = cache['cols%d' % i].reshape(-1, cache['cols%d' % i].shape[-1])
     gw = cols.T @ dzdot.reshape(-1, co)

@@ -67,6 +67,75 @@ def kink_free_slots(params, host, capacity, batch, rng, margin=1e-6, tries=64):
   raise AssertionError('no kink-free batch in %d draws' % tries)
 
 
+# Every step's bars of the pinned trajectories (tests/test_trajectory_gpu.py),
+# relative Frobenius norm per leaf: the update p_new - p_old, and mu / nu.
+STEP_UPDATE_BAR, STEP_MOMENT_BAR = 1e-4, 1e-5
+
+
+def f32_rmsprop(p, g, mu, nu, lr, decay, eps):
+  """optax 0.1.2 rmsprop(centered=True) of one leaf in numpy float32 (every
+  array argument is cast to float32); returns the new (p, mu, nu)."""
+  f = np.float32
+  p, g, mu, nu = (np.asarray(x, np.float64).astype(f) for x in (p, g, mu, nu))
+  lr, decay, eps, one = f(lr), f(decay), f(eps), f(1.0)
+  mm = (one - decay) * g + decay * mu
+  vv = (one - decay) * g * g + decay * nu
+  pn = p - lr * g / np.sqrt(vv - mm * mm + eps)
+  assert pn.dtype == f and mm.dtype == f and vv.dtype == f
+  return pn, mm, vv
+
+
+def f32_update_floor(p, mu, nu, ref, lr, decay, eps):
+  """What float32 storage alone costs one step's update, per leaf and from
+  the reference alone: float32 RMSProp (f32_rmsprop) from the same carried
+  state (p, mu, nu: float32 trees) and the fp64 oracle's own gradient
+  ref['grads'] correctly rounded to float32, measured exactly as the
+  implementation under test is, as the relative Frobenius error of p_new -
+  p_old against the oracle's fp64 update (ref['params']).  What remains is
+  the rounding of the moments, of the update and, most of it, of the stored
+  p_new (half an ulp of p per element, beside an update of lr g / sqrt(D)).
+  Returns ({'module/name': error}, {module: {name: float32 p_new}})."""
+  p_new = {m: {n: f32_rmsprop(p[m][n], ref['grads'][m][n], mu[m][n], nu[m][n], lr, decay,
+                              eps)[0] for n in p[m]} for m in p}
+  return tree_rel_errs(tree_delta(p_new, p), tree_delta(ref['params'], p)), p_new
+
+
+def tree_rel_errs(got, want):
+  """Per-leaf relative Frobenius-norm errors of a parameter tree, as
+  {'module/name': error}."""
+  out = {}
+  for m in want:
+    for n in want[m]:
+      w = np.asarray(want[m][n], np.float64)
+      d = np.linalg.norm(np.asarray(got[m][n], np.float64) - w)
+      out[m + '/' + n] = float(d / max(np.linalg.norm(w), 1e-30))
+  return out
+
+
+def tree_rel_err(got, want):
+  """Worst per-leaf relative Frobenius-norm error of a parameter tree."""
+  return max(tree_rel_errs(got, want).values())
+
+
+def tree_delta(a, b):
+  return {m: {n: np.asarray(a[m][n], np.float64) - np.asarray(b[m][n], np.float64)
+              for n in b[m]} for m in b}
+
+
+def decision_flips(masks, select, ref):
+  """How many of an implementation's discrete decisions in one learner step
+  differ from the unpinned fp64 oracle's (`ref`, a learner_ref.learner_step
+  result): ReLU units of the online(s_tm1) pass (`masks`, four boolean
+  arrays) and, for double-Q / PER, selected actions (`select`, or None)."""
+  units = sum(int(np.count_nonzero(np.asarray(m, bool).reshape(r.shape) != r))
+              for m, r in zip(masks, ref['masks']))
+  actions = 0
+  if select is not None:
+    actions = int(np.count_nonzero(
+        np.asarray(select) != np.argmax(ref['q_selector_t'], axis=1)))
+  return units, actions
+
+
 def canonical_chunk_sums(t):
   """Restatement of the device's chunk sums (sampling.hpp chunk_sum): per
   chunk of 4096 terms, lane l sums terms [16 l, 16 l + 16) in order, a

@@ -113,10 +113,14 @@ def _rel_norm_err(got, want):
 def test_learner_step_on_unfiltered_batches(device, algo):
   """Plain rng.integers batches (no kink filter, helpers.kink_free_slots):
   a ReLU pre-activation within f32 rounding of 0 may take the other branch
-  than in fp64, which moves single gradient entries (not the forward), so
-  q / td / loss keep their elementwise bars and the gradient (mu after one
-  step from zero state is (1 - decay) g) and the update are held to a
-  relative Frobenius-norm bar per leaf."""
+  than in fp64 (and a double-Q near-tie select the other action), which
+  moves a whole unit's gradient contribution.  The oracle is therefore
+  stepped with the device's own ReLU masks and selection
+  (Learner.fetch_activations; learner_ref.learner_step masks= / select=,
+  tests/test_mask_pinned_cpu.py), and the gradient (mu after one step from
+  zero state is (1 - decay) g) and the update are held to relative
+  Frobenius-norm bars per leaf: 1e-5 and 1e-4, the every-step bars of
+  tests/test_trajectory_gpu.py."""
   batch = 32
   for seed in (21, 22, 23, 24):
     net, lrn, st, host, online, target, mu, nu = _setup(algo, batch, seed=seed)
@@ -124,11 +128,17 @@ def test_learner_step_on_unfiltered_batches(device, algo):
         0, st.capacity, size=batch).astype(np.int32)
     s_tm1 = helpers.stacks_from(host['frames'], host['fidx'], slots, 0)
     s_t = helpers.stacks_from(host['frames'], host['fidx'], slots, 1)
-    ref = learner_ref.learner_step(
-        online, target, mu, nu, s_tm1, host['action'][slots],
-        host['reward'][slots], host['discount'][slots], s_t, algo=algo)
     lrn.step(st, torch.from_numpy(slots).to(device))
     q, td, loss = lrn.fetch_outputs()
+    act = lrn.fetch_activations(0)
+    masks = [act[k].cpu().numpy() > 0 for k in ('y1', 'y2', 'y3', 'h1')]
+    select = None
+    if algo != 'dqn':  # first maximum, as head.hpp's selection loop
+      select = np.argmax(lrn.fetch_activations(2)['q'].cpu().numpy(), axis=1)
+    ref = learner_ref.learner_step(
+        online, target, mu, nu, s_tm1, host['action'][slots],
+        host['reward'][slots], host['discount'][slots], s_t, algo=algo,
+        masks=masks, select=select)
     torch.cuda.synchronize()
     np.testing.assert_allclose(q.cpu().numpy(), ref['q_tm1'], atol=Q_ATOL)
     np.testing.assert_allclose(td.cpu().numpy(), ref['td'], atol=Q_ATOL)
@@ -143,11 +153,11 @@ def test_learner_step_on_unfiltered_batches(device, algo):
     u_err = _rel_norm_err(delta_got, delta_want)
     print('seed %d margin %.2e: gradient rel err %.2e, update rel err %.2e' % (
         seed, learner_ref.relu_margin(online, s_tm1), g_err, u_err))
-    # measured (round 3, seeds 21-24, margins 1.3e-7 .. 6.4e-7 — inside the
-    # 1e-6 band the filtered tests exclude): gradient <= 4.3e-7, update
-    # <= 3.6e-5
+    # (round 3, unpinned, seeds 21-24, margins 1.3e-7 .. 6.4e-7 — inside the
+    # 1e-6 band the filtered tests exclude: gradient <= 4.3e-7, update
+    # <= 3.6e-5)
     assert g_err <= 1e-5, g_err
-    assert u_err <= 1e-3, u_err
+    assert u_err <= 1e-4, u_err
 
 
 def test_forward_q_values_direct_and_slots(device):

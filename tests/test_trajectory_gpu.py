@@ -1,5 +1,7 @@
 """GPU parity over long trajectories: 50 carried-state steps per algorithm
-against the fp64 oracle stepped in lockstep.
+against the fp64 oracle stepped in lockstep, with the
+device's own discrete decisions pinned in the oracle (VERDICT r06 "Next
+round" item 2).
 
 Every step feeds the device and the oracle the same replay slots, drawn
 unfiltered (plain rng draws, no kink filter).  The oracle is stepped from
@@ -8,27 +10,49 @@ tree, for MGSC the logits and the Adam moments): a free-running fp64
 trajectory is not a usable reference here, because a ReLU pre-activation
 within f32 rounding of 0 can take the other branch than in fp64, and when
 that unit's parameters carry a near-zero centered-RMSProp denominator the
-two updates differ by O(lr) at once.  An independent f32 implementation
-(oracle/torch_cpu.py, the same 50 batches on CPU) stays within 1e-5 of the
-fp64 trajectory for 40 steps and then leaves it (9e-4 at step 45, 1.3e-2 at
-step 50), so a bar on the end state of free-running
-trajectories would test the seed, not the kernels.  Stepping from the
-device's state checks every one of the 50 updates, with realistic carried
-moments (nu - mu^2 small under the sqrt) and a target sync in the middle
-(dqn/agent.py:155-156), at the single-step bars:
+two updates differ by O(lr) at once.  Stepping from the device's state
+checks every one of the 50 updates, with realistic carried moments (nu -
+mu^2 small under the sqrt) and a target sync in the middle
+(dqn/agent.py:155-156).
 
-  q, td: atol 1e-4; loss rtol 1e-4 (every step);
-  update p_new - p_old, mu, nu, per leaf, relative Frobenius norm: the
-  median step <= 1e-4 (update) / 1e-5 (mu, nu), every step <= 1e-2 / 3e-3.
+The same discontinuity would make a single step incomparable too: on an
+unfiltered batch one ReLU unit of the online(s_tm1) pass can fall on the
+other side of 0 on the device than in fp64, or (double-Q, PER) a near-tie
+of the online argmax at s_t can select the other action, and then the
+step's gradient differs in a whole unit's contribution.  So after the
+device step the test reads the device's four post-ReLU activations of copy
+0 and, for double-Q / PER, its online q(s_t) (Learner.fetch_activations),
+forms masks = y > 0 and select = argmax (first maximum, as head.hpp) and
+steps the oracle with them (learner_ref.learner_step masks= / select=;
+tests/test_mask_pinned_cpu.py checks the pinning and that an independent
+f32 implementation then meets these bars on every step).  What is left is
+rounding, and every step is held to one level:
 
-The two-level bar is the discontinuity again: the batch is unfiltered, so a
-step can carry a kink flip (or, for double-Q, a near-tie of the online
-argmax at s_t that picks the other action's target) and then its gradient
-differs in whole units.  The independent f32 implementation from the same
-fp64 states on the same batches (round 6, CPU) shows exactly that: typical
-steps 2-5e-5 (update) and 1-6e-7 (mu, nu), worst double-Q step 4.8e-3 /
-1.3e-3 / 4.8e-4.  A step above 1e-4 prints its ReLU margin (oracle
-relu_margin) so the cause can be read off the log.
+  q, td: atol 1e-4; loss rtol 1e-4;
+  update p_new - p_old per leaf, relative Frobenius norm <= 1e-4;
+  mu, nu per leaf <= 1e-5.
+
+One exception, not a kink: PER's optimizer (prioritized/run_atari.py) has a
+quarter of the learning rate, so the float32 rounding of the stored
+parameter (half an ulp of p per element) is four times as large beside its
+update, and on the one-element shared-bias leaf nothing averages it (on a
+step where that leaf's update is 8e-7 beside a parameter of 0.039, half an
+ulp of the parameter is 2e-3 of the update).  No float32 implementation can
+meet 1e-4 there, so on the PER trajectory each leaf's bar on each step is
+the larger of 1e-4 and twice what float32 storage alone costs from that
+same state: float32 RMSProp of the oracle's own fp64 gradient, correctly
+rounded, from the device's carried p, mu, nu (helpers.f32_update_floor),
+measured like the device's update.  The 2x is the margin an independent
+f32 implementation has under 1e-4 on the double-Q trajectory
+(tests/test_mask_pinned_cpu.py).  That bar comes from the oracle and the
+state alone; a leaf whose floor is below 5e-5 keeps 1e-4; every such step
+prints both figures and how many stored elements differ from that
+replay's.  The median step stays within 1e-4, mu and nu keep 1e-5, and the
+other four trajectories have no exception.
+
+Each trajectory prints how many decisions differed from the unpinned oracle
+and on which steps, and for those steps the unpinned error beside the pinned
+one.
 
 PER also checks the sum tree after every priority write-back
 (prioritized/agent.py:187-206), MGSC the logits and the Adam moments after
@@ -48,23 +72,10 @@ pytestmark = pytest.mark.gpu
 
 STEPS = 50
 SYNC_AT = 25  # target <- online after this step's learn
-UPDATE_MEDIAN, MOMENT_MEDIAN = 1e-4, 1e-5
-UPDATE_BAR, MOMENT_BAR = 1e-2, 3e-3
+STEP_UPDATE_BAR, STEP_MOMENT_BAR = helpers.STEP_UPDATE_BAR, helpers.STEP_MOMENT_BAR
 
-
-def _rel_err(got, want):
-  worst = 0.0
-  for m in want:
-    for n in want[m]:
-      w = np.asarray(want[m][n], np.float64)
-      d = np.linalg.norm(np.asarray(got[m][n], np.float64) - w)
-      worst = max(worst, d / max(np.linalg.norm(w), 1e-30))
-  return worst
-
-
-def _delta(a, b):
-  return {m: {n: np.asarray(a[m][n], np.float64) - np.asarray(b[m][n], np.float64)
-              for n in b[m]} for m in b}
+_rel_err = helpers.tree_rel_err
+_delta = helpers.tree_delta
 
 
 def _setup(algo, seed, capacity=256, num_frames=640, a=6, optimizer=None):
@@ -101,35 +112,52 @@ def _state(lrn):
 
 
 class _Worst:
-  """Every step's error of each kind (median and worst checked and printed
-  at the end)."""
+  """Every step's error of each kind, and the steps on which a decision of
+  the device differed from the unpinned oracle's; printed and checked at the
+  end, so a failing run still logs all of its steps.
 
-  def __init__(self):
+  f32_floor (the PER trajectory): a leaf's update bar on a step is the larger
+  of STEP_UPDATE_BAR and twice helpers.f32_update_floor of that leaf on that
+  step, which comes from the oracle and the carried state alone."""
+
+  def __init__(self, f32_floor=False):
     self.v = {}
+    self.leaf = {}  # leaf -> every step's (update error, bar)
+    self.flips = []  # (step, ReLU units, actions)
+    self.f32_floor = f32_floor
 
   def add(self, k, x):
     self.v.setdefault(k, []).append(float(x))
 
-  def median(self, k):
-    return float(np.median(self.v[k]))
+  def add_update(self, by_leaf, floor=None):
+    for k, x in by_leaf.items():
+      bar = STEP_UPDATE_BAR if floor is None else max(STEP_UPDATE_BAR, 2 * floor[k])
+      self.leaf.setdefault(k, []).append((x, bar))
+    self.add('update', max(by_leaf.values()))
 
   def report(self, label):
     print('%s over %d steps (median / worst): %s' % (
         label, STEPS, ', '.join('%s %.2e / %.2e' % (k, np.median(v), max(v))
                                 for k, v in sorted(self.v.items()))))
-    if 'update' in self.v:
-      assert self.median('update') <= UPDATE_MEDIAN, self.median('update')
-      assert self.median('mu') <= MOMENT_MEDIAN, self.median('mu')
-      assert self.median('nu') <= MOMENT_MEDIAN, self.median('nu')
+    print('%s: %d ReLU unit(s) and %d selected action(s) differed from the unpinned '
+          'oracle, on steps %s' % (label, sum(f[1] for f in self.flips),
+                                   sum(f[2] for f in self.flips), [f[0] for f in self.flips]))
+    for k, v in self.leaf.items():
+      over = [(i, x, bar) for i, (x, bar) in enumerate(v) if not x <= bar]
+      assert not over, '%s: update of %s above its bar on (step, error, bar) %s' % (label, k, over)
+    assert np.median(self.v['update']) <= STEP_UPDATE_BAR, (label, np.median(self.v['update']))
+    for k in ('mu', 'nu'):
+      over = [(i, x) for i, x in enumerate(self.v[k]) if not x <= STEP_MOMENT_BAR]
+      assert not over, '%s: %s above %.0e on (step, error) %s' % (label, k, STEP_MOMENT_BAR, over)
 
 
 def _learn_and_check(lrn, st, host, slots, device, worst, algo='dqn', weights=None,
                      write_back=None, lr=2.5e-4, eps=0.01 / 32**2):
   """One device step from its carried state against one oracle step from the
-  same state; returns the oracle's result."""
+  same state with the device's ReLU masks and action selection; returns the
+  oracle's result."""
   p, t, mu, nu = _state(lrn)
-  ref = learner_ref.learner_step(p, t, mu, nu, *_batch(host, slots), algo=algo,
-                                 weights=weights, lr=lr, eps=eps)
+  batch = _batch(host, slots)
   slots_d = torch.from_numpy(slots).to(device)
   w_d = None if weights is None else torch.from_numpy(weights).to(device)
   if write_back is not None:
@@ -137,22 +165,52 @@ def _learn_and_check(lrn, st, host, slots, device, worst, algo='dqn', weights=No
   else:
     lrn.step(st, slots_d, w_d)
   q, td, loss = [x.cpu().numpy() for x in lrn.fetch_outputs()]
+  act = lrn.fetch_activations(0)
+  masks = [act[k].cpu().numpy() > 0 for k in ('y1', 'y2', 'y3', 'h1')]
+  select = None
+  if algo != 'dqn':  # first maximum, as head.hpp's selection loop
+    select = np.argmax(lrn.fetch_activations(2)['q'].cpu().numpy(), axis=1)
+  kw = dict(algo=algo, weights=weights, lr=lr, eps=eps)
+  ref = learner_ref.learner_step(p, t, mu, nu, *batch, masks=masks, select=select, **kw)
   np.testing.assert_allclose(q, ref['q_tm1'], atol=1e-4)
   np.testing.assert_allclose(td, ref['td'], atol=1e-4)
   np.testing.assert_allclose(loss[0], ref['loss'], rtol=1e-4, atol=1e-7)
   worst.add('td', np.abs(td - ref['td']).max())
   p1, t1, mu1, nu1 = _state(lrn)
-  ue = _rel_err(_delta(p1, p), _delta(ref['params'], p))
-  me, ne = _rel_err(mu1, ref['mu']), _rel_err(nu1, ref['nu'])
-  worst.add('update', ue)
+
+  def errs(r):
+    by_leaf = helpers.tree_rel_errs(_delta(p1, p), _delta(r['params'], p))
+    return by_leaf, (max(by_leaf.values()), _rel_err(mu1, r['mu']), _rel_err(nu1, r['nu']))
+
+  by_leaf, (ue, me, ne) = errs(ref)
+  step = len(worst.v.get('update', ()))
+  floor = None
+  if worst.f32_floor:
+    floor, p_f32 = helpers.f32_update_floor(p, mu, nu, ref, lr, 0.95, eps)
+    for k in by_leaf:
+      if max(by_leaf[k], floor[k]) > STEP_UPDATE_BAR:
+        m, n = k.rsplit('/', 1)
+        print('  step %d %s: update error %.2e on the device, %.2e for float32 RMSProp of the '
+              "oracle's gradient from the same state (%d of %d stored elements differ)" % (
+                  step, k, by_leaf[k], floor[k],
+                  np.count_nonzero(p1[m][n] != p_f32[m][n]), p1[m][n].size))
+  worst.add_update(by_leaf, floor)
   worst.add('mu', me)
   worst.add('nu', ne)
-  if max(ue, 10 * me, 10 * ne) > 1e-4:
-    print('  step with update %.2e mu %.2e nu %.2e: ReLU margin of its batch %.1e' % (
-        ue, me, ne, learner_ref.relu_margin(p, _batch(host, slots)[0])))
-  assert ue <= UPDATE_BAR, ue
-  assert me <= MOMENT_BAR, me
-  assert ne <= MOMENT_BAR, ne
+  # the unpinned oracle's decisions: its own masks of the online(s_tm1) pass
+  # (the selector pass at s_t is not pinned, so ref's is the unpinned one)
+  _, cache = learner_ref.forward(p, batch[0], algo != 'dqn')
+  units, actions = helpers.decision_flips(
+      masks, select, dict(masks=cache['masks'], q_selector_t=ref['q_selector_t']))
+  if units or actions:
+    worst.flips.append((step, units, actions))
+    free = errs(learner_ref.learner_step(p, t, mu, nu, *batch, **kw))[1]
+    print('  step %d: %d ReLU unit(s), %d action(s) differ from the unpinned oracle; update / '
+          'mu / nu unpinned %.2e / %.2e / %.2e, pinned %.2e / %.2e / %.2e' % (
+              (step, units, actions) + free + (ue, me, ne)))
+  elif ue > STEP_UPDATE_BAR or me > STEP_MOMENT_BAR or ne > STEP_MOMENT_BAR:
+    print('  step %d without a flip: update %.2e (%s) mu %.2e nu %.2e' % (
+        step, ue, max(by_leaf, key=by_leaf.get), me, ne))
   for m in t:  # a learner step leaves the target alone
     for n in t[m]:
       np.testing.assert_array_equal(t1[m][n], t[m][n])
@@ -206,7 +264,7 @@ def test_fifty_step_per_trajectory_with_tree(device):
       _native.ptr(torch.from_numpy(leaves0).to(device)), cap, _native.stream_handle()))
   max_seen = torch.ones((1,), dtype=torch.float64, device=device)
   active = np.arange(cap)
-  worst = _Worst()
+  worst = _Worst(f32_floor=True)
   for step in range(STEPS):
     torch.cuda.synchronize()
     before = tree.cpu().numpy()
