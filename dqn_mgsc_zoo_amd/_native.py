@@ -159,6 +159,10 @@ SIGNATURES = {
         _int,
         [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
          ctypes.c_uint64, _vp, _vp, _vp, _vp]),
+    'dqz_learner_step_logits_exact': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
+         ctypes.c_uint64, _vp, _vp, _vp, _vp]),
     'dqz_learner_step_per_draw': (
         _int,
         [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore),

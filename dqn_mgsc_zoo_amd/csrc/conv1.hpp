@@ -21,11 +21,13 @@ struct Conv1Src {
   const uint8_t* states;  // direct uint8 [B][84][84][4] input, or null
   int fused;              // 1: slots come from the fused uniform sampler `draw`;
                           // 2: from the fused learned-logit draw `sm`;
-                          // 3: from the fused prioritized draw `per`
+                          // 3: from the fused prioritized draw `per`;
+                          // 4: from the fused exact learned-logit draw `smx`
   union {                 // one draw per launch: the kernel argument stays small
     UniformDraw draw;
     SoftmaxDraw sm;
     PerSampleArgs per;
+    SoftmaxDrawExact smx;
   };
   // Batch record: block (rb 0, z 0) of sample b also copies action / reward /
   // discount of its slot into rec[b] = {a as int bits, r, d, 0}, so the head
@@ -154,6 +156,9 @@ __device__ __forceinline__ void stage_conv1_input(uint16_t* s_in, const Conv1Src
       const PerDrawOut d = per_draw_slot(src.per, b, reinterpret_cast<double*>(s_in), rb == 0 && z == 0);
       slot = d.slot;
       per_prob = d.prob;
+    } else if constexpr (F == 4) {  // fused exact learned-logit draw: numpy's own float32 terms
+      slot = softmax_draw_slot_exact(src.smx, b);
+      if (threadIdx.x == 0 && rb == 0 && z == 0) src.smx.slots_out[b] = slot;
     } else {
       slot = src.slots[b];
     }

@@ -97,13 +97,15 @@ int dqz_gather_stacks(const dqz_store* S, const int32_t* slots, int n, int which
 struct dqz_logit_buffer {
   int64_t capacity;
   int nblocks, max_queries;
-  void* block;  // double csum[nblocks] | MaxSum part[nblocks] | int dirty[nblocks] | float lse | LogitRun | sync
+  void* block;  // double csum[nblocks] | MaxSum part[nblocks] | int dirty[nblocks] | float lse | LogitRun | sync |
+                // exact mode: double csum_x[nblocks] | float part_x[nblocks] | bsum_x[nbuf] | scal_x[2] | programs
   double* csum;    // per-chunk sums of the sampling terms (sampling.hpp chunk_sum)
   MaxSum* part;
   int* dirty;      // chunks a writer changed, for chunk_sums_kernel
   float* lse;
   LogitRun* run;   // running log-sum-exp (sampling.hpp)
-  int* sync;       // softmax_sample_kernel's done word (SampleSync)
+  int* sync;       // (x SampleSync::kStride) [1] softmax_sample_kernel's done word, [3] / [4] the arrival
+                   // tickets of the exact preparation's first / second launch (npx_take_ticket)
   // exact mode (dqz_logits_sample_exact): chunk sums of the exact terms,
   // chunk maxima, numpy-buffer sums, {c, lse}
   int nbuf;
@@ -161,6 +163,11 @@ static std::vector<int> npx_program(int L) {
   return prog;
 }
 
+// 256-byte lines of a logit buffer's sync words: softmax_sample_kernel's three,
+// then one per arrival ticket of the exact preparation.
+constexpr int kLogitSyncLines = 5;
+constexpr int kNpxTicketMax = 3, kNpxTicketSum = 4;
+
 // Running adds between full re-scans of a logit buffer (bounds the running
 // sum's drift; each scan reads the whole buffer once).
 constexpr int kLogitReseed = 4096;
@@ -175,7 +182,7 @@ int dqz_logit_buffer_create(int64_t capacity, int max_queries, dqz_logit_buffer*
   const size_t head = (size_t)b->nblocks * (sizeof(MaxSum) + sizeof(double) + sizeof(int));
   const size_t sync_off = (head + 64 + sizeof(LogitRun) + 255) / 256 * 256;
   b->nbuf = (int)((capacity + NPX_BUF - 1) / NPX_BUF);
-  const size_t x_off = sync_off + 3 * SampleSync::kStride * sizeof(int);  // 256-aligned
+  const size_t x_off = sync_off + kLogitSyncLines * SampleSync::kStride * sizeof(int);  // 256-aligned
   const size_t prog_off = (x_off + (size_t)b->nblocks * (sizeof(double) + sizeof(float)) + (size_t)b->nbuf * sizeof(float) +
                             64 + 255) / 256 * 256;
   const size_t bytes = prog_off + 2 * NPX_PROG * sizeof(int);
@@ -368,16 +375,24 @@ int dqz_logits_sample_slots(dqz_logit_buffer* b, const float* logits, uint64_t s
   return logits_sample_impl(b, logits, seed, counter_dev, uniforms, n, out_slots, out_idx, (hipStream_t)stream);
 }
 
-// numpy's float32 logsumexp of the whole buffer -> b->scal_x[1] (c in [0])
+// numpy's float32 logsumexp of the whole buffer -> b->scal_x[1] (c in [0]):
+// two launches, each finished by its last workgroup to arrive.
 static int npx_lse(dqz_logit_buffer* b, const float* logits, hipStream_t st) {
-  hipLaunchKernelGGL(npx_max_kernel, dim3(b->nblocks), dim3(SM_THREADS), 0, st, logits, b->capacity, b->part_x);
-  DQZ_HIP(hipGetLastError());
-  hipLaunchKernelGGL(npx_cmax_kernel, dim3(1), dim3(SM_THREADS), 0, st, b->part_x, b->nblocks, b->scal_x);
+  hipLaunchKernelGGL(npx_max_kernel, dim3(b->nblocks), dim3(SM_THREADS), 0, st, logits, b->capacity, b->part_x,
+                     b->scal_x, b->sync + kNpxTicketMax * SampleSync::kStride);
   DQZ_HIP(hipGetLastError());
   hipLaunchKernelGGL(npx_bufsum_kernel, dim3(b->nbuf), dim3(SM_THREADS), 0, st, logits, b->capacity, b->scal_x,
-                     b->bsum_x, b->prog_full, b->prog_last);
+                     b->bsum_x, b->prog_full, b->prog_last, b->sync + kNpxTicketSum * SampleSync::kStride);
   DQZ_HIP(hipGetLastError());
-  hipLaunchKernelGGL(npx_lse_kernel, dim3(1), dim3(64), 0, st, b->bsum_x, b->nbuf, b->scal_x);
+  return DQZ_OK;
+}
+
+// The exact mode's preparation, three launches: the logsumexp, then the
+// chunk sums of p = np_expf(x - lse) -> b->csum_x (and p itself, if asked).
+static int npx_prepare(dqz_logit_buffer* b, const float* logits, float* p_out, hipStream_t st) {
+  if (int rc = npx_lse(b, logits, st)) return rc;
+  hipLaunchKernelGGL(npx_chunk_kernel, dim3(b->nblocks), dim3(SM_THREADS), 0, st, logits, b->capacity, b->scal_x,
+                     b->csum_x, p_out);
   DQZ_HIP(hipGetLastError());
   return DQZ_OK;
 }
@@ -407,10 +422,7 @@ int dqz_logits_sample_exact(dqz_logit_buffer* b, const float* logits, const doub
   if (n < 0 || n > 65535) return fail(DQZ_ERR_INVALID, "n out of range");
   if (n > 0 && (!uniforms || !out_idx)) return fail(DQZ_ERR_INVALID, "null argument");
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = npx_lse(b, logits, st)) return rc;
-  hipLaunchKernelGGL(npx_chunk_kernel, dim3(b->nblocks), dim3(SM_THREADS), 0, st, logits, b->capacity, b->scal_x,
-                     b->csum_x, p_out);
-  DQZ_HIP(hipGetLastError());
+  if (int rc = npx_prepare(b, logits, p_out, st)) return rc;
   if (n > 0) {
     hipLaunchKernelGGL(npx_sample_kernel, dim3(n), dim3(SM_THREADS), 0, st, logits, b->capacity, b->scal_x, b->csum_x,
                        b->nblocks, uniforms, out_idx);
@@ -454,6 +466,25 @@ int dqz_learner_step_logits(dqz_learner* L, const dqz_params* P, const dqz_store
   SoftmaxDraw sm{logits, buf->capacity, buf->run, buf->csum, buf->nblocks,
                  seed,   uniforms ? nullptr : counter_dev,    uniforms,  slots_out};
   return step_impl(L, P, S, slots_out, nullptr, stream, kNoProfile, nullptr, nullptr, nullptr, 0, 0, nullptr, &sm);
+}
+
+int dqz_learner_step_logits_exact(dqz_learner* L, const dqz_params* P, const dqz_store* S, dqz_logit_buffer* buf,
+                                  const float* logits, uint64_t seed, uint64_t* counter_dev, const double* uniforms,
+                                  int32_t* slots_out, void* stream) {
+  if (!L || !buf || !logits || !slots_out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (!counter_dev == !uniforms) return fail(DQZ_ERR_INVALID, "give exactly one of counter_dev and uniforms");
+  if (L->cfg.algo == DQZ_ALGO_PER) return fail(DQZ_ERR_INVALID, "PER samples by priority, not by learned logits");
+  if (buf->capacity > INT32_MAX) return fail(DQZ_ERR_INVALID, "int32 slots need capacity < 2^31");
+  // the step's own checks first: nothing is enqueued for a call that fails
+  if (!P || !P->online || !P->target) return fail(DQZ_ERR_INVALID, "null argument");
+  if (!P->mu || !P->nu) return fail(DQZ_ERR_INVALID, "null optimizer state");
+  if (int rc = check_store(S)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = npx_prepare(buf, logits, nullptr, st)) return rc;
+  SoftmaxDrawExact smx{logits, buf->capacity, buf->scal_x, buf->csum_x, buf->nblocks,
+                       seed,   counter_dev,   uniforms,    slots_out};
+  return step_impl(L, P, S, slots_out, nullptr, stream, kNoProfile, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, &smx);
 }
 
 int dqz_uniform_philox(uint64_t seed, uint64_t* counter_dev, int n, double* out, void* stream) {

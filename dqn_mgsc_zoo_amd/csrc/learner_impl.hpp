@@ -100,6 +100,7 @@ int step_impl(dqz_learner* L, const dqz_params* P, const dqz_store* S, const int
               const float* meta_p = nullptr, const UniformDraw* draw = nullptr, int unit = 0,
               int gacc = 0, const PerWbArgs* wb = nullptr, const SoftmaxDraw* sm = nullptr,
               const PerSampleArgs* pd = nullptr, const Rms* meta_epi = nullptr,
-              const HeadArgs* meta_sm = nullptr, uint8_t* xout = nullptr);
+              const HeadArgs* meta_sm = nullptr, uint8_t* xout = nullptr,
+              const SoftmaxDrawExact* smx = nullptr);
 
 }  // namespace dqz

@@ -27,7 +27,8 @@ static int g_attr_done = 0;
 static int init_kernel_attrs() {
   if (g_attr_done) return DQZ_OK;
   const void* fwd_kernels[] = {(const void*)fwd_conv_kernel<0>, (const void*)fwd_conv_kernel<1>,
-                               (const void*)fwd_conv_kernel<2>, (const void*)fwd_conv_kernel<3>};
+                               (const void*)fwd_conv_kernel<2>, (const void*)fwd_conv_kernel<3>,
+                               (const void*)fwd_conv_kernel<4>};
   for (const void* k : fwd_kernels)
     DQZ_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kConv1FwdSmem));
   g_attr_done = 1;
@@ -175,6 +176,7 @@ static int forward_impl(dqz_learner* L, const NetZ& nz, int Z, int B, const Conv
     case 1: hipLaunchKernelGGL(fwd_conv_kernel<1>, grid, dim3(256), kConv1FwdSmem, st, c1, c2, c3); break;
     case 2: hipLaunchKernelGGL(fwd_conv_kernel<2>, grid, dim3(256), kConv1FwdSmem, st, c1, c2, c3); break;
     case 3: hipLaunchKernelGGL(fwd_conv_kernel<3>, grid, dim3(256), kConv1FwdSmem, st, c1, c2, c3); break;
+    case 4: hipLaunchKernelGGL(fwd_conv_kernel<4>, grid, dim3(256), kConv1FwdSmem, st, c1, c2, c3); break;
     default: hipLaunchKernelGGL(fwd_conv_kernel<0>, grid, dim3(256), kConv1FwdSmem, st, c1, c2, c3); break;
   } DQZ_HIP(hipGetLastError()));
   if (pe.on()) pe.ms[1] = pe.ms[2] = 0.f;
@@ -220,7 +222,8 @@ static HeadArgs make_head(dqz_learner* L, const NetZ& nz, int Z, int B) {
 int dqz::step_impl(dqz_learner* L, const dqz_params* P, const dqz_store* S, const int32_t* slots,
                    const float* is_weights, void* stream, PhaseEvents pe, float* gout, const float* meta_p,
                    const UniformDraw* draw, int unit, int gacc, const PerWbArgs* wb, const SoftmaxDraw* sm,
-                   const PerSampleArgs* pd, const Rms* meta_epi, const HeadArgs* meta_sm, uint8_t* xout) {
+                   const PerSampleArgs* pd, const Rms* meta_epi, const HeadArgs* meta_sm, uint8_t* xout,
+                   const SoftmaxDrawExact* smx) {
   if (!L || !P || !P->online || !P->target || !slots) return fail(DQZ_ERR_INVALID, "null argument");
   if (!gout && !meta_epi && (!P->mu || !P->nu)) return fail(DQZ_ERR_INVALID, "null optimizer state");
   if (meta_epi && meta_epi->meta == 1 && (!P->mu || !P->nu)) return fail(DQZ_ERR_INVALID, "null optimizer state");
@@ -241,7 +244,7 @@ int dqz::step_impl(dqz_learner* L, const dqz_params* P, const dqz_store* S, cons
   src.discount = S->discount;
   src.rec = reinterpret_cast<float4*>(L->rec);
   src.xout = xout;
-  if (draw || sm || pd) {  // conv1 draws the batch itself; later kernels read the published slots
+  if (draw || sm || pd || smx) {  // conv1 draws the batch itself; later kernels read the published slots
     Conv1Src fsrc = src;
     if (draw) {
       fsrc.fused = 1;
@@ -250,6 +253,9 @@ int dqz::step_impl(dqz_learner* L, const dqz_params* P, const dqz_store* S, cons
       fsrc.fused = 3;
       fsrc.per = *pd;
       fsrc.per.out_wb = L->per_wb;
+    } else if (smx) {
+      fsrc.fused = 4;
+      fsrc.smx = *smx;
     } else {
       fsrc.fused = 2;
       fsrc.sm = *sm;
@@ -292,7 +298,11 @@ int dqz::step_impl(dqz_learner* L, const dqz_params* P, const dqz_store* S, cons
     h.meta_p_out = meta_sm->meta_p_out;
   }
   h.rec = reinterpret_cast<const float4*>(L->rec);
-  h.advance = draw ? draw->counter : sm ? sm->counter : pd ? (pd->inj_u ? nullptr : pd->counter) : nullptr;
+  h.advance = draw  ? draw->counter
+              : sm  ? sm->counter
+              : smx ? smx->counter
+              : pd  ? (pd->inj_u ? nullptr : pd->counter)
+                    : nullptr;
   h.unit = unit;
   h.bound = L->cfg.grad_error_bound;
   h.td = L->td;

@@ -757,8 +757,11 @@ DQZ_OTHER_KERNEL __launch_bounds__(SM_THREADS) void softmax_sample_kernel(
 // choice then sums the float64 terms in this file's chunk order, not
 // numpy's sequential cumsum: the two CDFs differ by float64 rounding (~1e-16
 // relative), so a draw can differ only for a uniform that close to a step.
-// Passes: chunk maxima, c, per-buffer pairwise sums, lse, the exact chunk
-// sums, the draws: six launches, each a pass over the buffer at most.
+// Passes: chunk maxima (-> c), per-buffer pairwise sums (-> lse), the exact
+// chunk sums: three preparation launches, each a pass over the buffer; then
+// the draws, in a launch of their own (npx_sample_kernel) or inside the
+// learner's conv1 workgroups (SoftmaxDrawExact).  The two scalars are formed
+// by the last workgroup of their launch to arrive (npx_take_ticket).
 
 __device__ __forceinline__ float np_expf(float x) {
 #pragma clang fp contract(off)
@@ -811,9 +814,36 @@ constexpr int NPX_BUF = 8192;   // np.getbufsize(): the reduction's buffer
 constexpr int NPX_LEAF = 128;   // numpy's PW_BLOCKSIZE
 constexpr int NPX_MAXLEAF = 256;
 
-// chunk maxima (np.max is order-free)
+// Arrival ticket of the launches below.  Thread 0 publishes the workgroup's
+// partial write-through, drains the store, and takes a ticket; the workgroup
+// that draws count - 1 (returns true to all of its threads) finds every
+// partial published, reads them with load_fresh_f32 and finishes the pass.
+// Nobody waits for anybody: a ticket, not a barrier.  The finisher resets the
+// word (npx_reset_ticket), so the next launch and graph replays start clean.
+__device__ __forceinline__ float load_fresh_f32(const float* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ bool npx_take_ticket(float* slot, float v, int* ticket, int count) {
+  __shared__ int s_last;
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(slot, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    s_last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == count - 1;
+  }
+  __syncthreads();
+  return s_last != 0;
+}
+
+__device__ __forceinline__ void npx_reset_ticket(int* ticket) {
+  __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// chunk maxima (np.max is order-free); the last workgroup to arrive reduces
+// them to c -> scal[0]
 DQZ_OTHER_KERNEL __launch_bounds__(SM_THREADS) void npx_max_kernel(const float* __restrict__ x, int64_t n,
-                                                              float* __restrict__ part) {
+                                                              float* __restrict__ part,
+                                                              float* __restrict__ scal, int* ticket) {
   __shared__ float sbuf[SM_THREADS / 64];
   float xv[SM_PER_LANE];
   load_chunk_lane(x, n, blockIdx.x, xv);
@@ -823,19 +853,18 @@ DQZ_OTHER_KERNEL __launch_bounds__(SM_THREADS) void npx_max_kernel(const float* 
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
   if ((threadIdx.x & 63) == 0) sbuf[threadIdx.x >> 6] = m;
   __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = fmaxf(fmaxf(sbuf[0], sbuf[1]), fmaxf(sbuf[2], sbuf[3]));
-}
-
-// c = max of the chunk maxima -> scal[0]
-DQZ_OTHER_KERNEL __launch_bounds__(SM_THREADS) void npx_cmax_kernel(const float* __restrict__ part, int nparts,
-                                                               float* __restrict__ scal) {
-  __shared__ float sbuf[SM_THREADS / 64];
-  float m = -INFINITY;
-  for (int k = threadIdx.x; k < nparts; k += SM_THREADS) m = fmaxf(m, part[k]);
+  m = fmaxf(fmaxf(sbuf[0], sbuf[1]), fmaxf(sbuf[2], sbuf[3]));
+  const int nparts = gridDim.x;
+  if (!npx_take_ticket(part + blockIdx.x, m, ticket, nparts)) return;
+  m = -INFINITY;
+  for (int k = threadIdx.x; k < nparts; k += SM_THREADS) m = fmaxf(m, load_fresh_f32(part + k));
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0) sbuf[threadIdx.x >> 6] = m;
+  if ((threadIdx.x & 63) == 0) sbuf[threadIdx.x >> 6] = m;  // every thread is past its first read (the ticket's barrier)
   __syncthreads();
-  if (threadIdx.x == 0) scal[0] = fmaxf(fmaxf(sbuf[0], sbuf[1]), fmaxf(sbuf[2], sbuf[3]));
+  if (threadIdx.x == 0) {
+    scal[0] = fmaxf(fmaxf(sbuf[0], sbuf[1]), fmaxf(sbuf[2], sbuf[3]));
+    npx_reset_ticket(ticket);
+  }
 }
 
 // One workgroup per 8192-element buffer.  numpy's recursion over a buffer
@@ -850,10 +879,9 @@ DQZ_OTHER_KERNEL __launch_bounds__(SM_THREADS) void npx_cmax_kernel(const float*
 constexpr int NPX_PROG = 1024;
 
 DQZ_OTHER_KERNEL __launch_bounds__(SM_THREADS) void npx_bufsum_kernel(const float* __restrict__ x, int64_t n,
-                                                                 const float* __restrict__ scal,
-                                                                 float* __restrict__ bsum,
+                                                                 float* scal, float* __restrict__ bsum,
                                                                  const int* __restrict__ prog_full,
-                                                                 const int* __restrict__ prog_last) {
+                                                                 const int* __restrict__ prog_last, int* ticket) {
   __shared__ int sp[NPX_PROG];
   __shared__ float s_val[2 * NPX_MAXLEAF];
   const bool partial = blockIdx.x == gridDim.x - 1 && n % NPX_BUF != 0;
@@ -897,15 +925,24 @@ DQZ_OTHER_KERNEL __launch_bounds__(SM_THREADS) void npx_bufsum_kernel(const floa
       s_val[p_ops[3 * k]] = s_val[p_ops[3 * k + 1]] + s_val[p_ops[3 * k + 2]];
     __syncthreads();
   }
-  if (threadIdx.x == 0) bsum[blockIdx.x] = s_val[root];
-}
-
-// np.sum = the buffer sums added in order; lse = c + log(sum) -> scal[1]
-DQZ_OTHER_KERNEL void npx_lse_kernel(const float* __restrict__ bsum, int nbuf, float* __restrict__ scal) {
-  if (threadIdx.x != 0) return;
+  // np.sum = the buffer sums added in order; lse = c + log(sum) -> scal[1],
+  // by the last workgroup to arrive: all threads fetch the sums (s_val's 512
+  // at a time), thread 0 adds them in index order.
+  const int nbuf = gridDim.x;
+  if (!npx_take_ticket(bsum + blockIdx.x, s_val[root], ticket, nbuf)) return;
   float s = 0.f;
-  for (int k = 0; k < nbuf; ++k) s = s + bsum[k];
-  scal[1] = scal[0] + np_logf(s);
+  for (int k0 = 0; k0 < nbuf; k0 += 2 * NPX_MAXLEAF) {
+    const int m = min(nbuf - k0, 2 * NPX_MAXLEAF);
+    for (int k = threadIdx.x; k < m; k += SM_THREADS) s_val[k] = load_fresh_f32(bsum + k0 + k);
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int k = 0; k < m; ++k) s = s + s_val[k];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    scal[1] = c + np_logf(s);
+    npx_reset_ticket(ticket);
+  }
 }
 
 // The exact terms p = np_expf(x - lse) per chunk: their float64 chunk sums
@@ -955,6 +992,30 @@ DQZ_OTHER_KERNEL __launch_bounds__(SM_THREADS) void npx_sample_kernel(const floa
   const int64_t idx = softmax_choice_terms(
       x, n, [lse](float v) { return (double)np_expf(v - lse); }, csum, nblocks, [&] { return uniforms[q]; });
   if (threadIdx.x == 0) out_idx[q] = idx;
+}
+
+// The exact draw fused into the learner's forward launch
+// (dqz_learner_step_logits_exact): SoftmaxDraw with the exact mode's scalars
+// ({c, lse}) and chunk sums in place of the running state's, field for field,
+// so Conv1Src's union does not grow.
+struct SoftmaxDrawExact {
+  const float* x;         // logits [n]
+  int64_t n;
+  const float* scal;      // {c, lse} of the three preparation launches
+  const double* csum;     // [nblocks] chunk sums of the exact terms
+  int nblocks;
+  uint64_t seed;
+  uint64_t* counter;      // Philox step counter (null when `uniforms` is set)
+  const double* uniforms;  // the caller's uniforms [B], or null
+  int32_t* slots_out;     // [B]: block (rb 0, z 0) of sample b publishes its slot
+};
+static_assert(sizeof(SoftmaxDrawExact) == sizeof(SoftmaxDraw), "Conv1Src's union stays its size");
+
+__device__ __forceinline__ int32_t softmax_draw_slot_exact(const SoftmaxDrawExact& d, int b) {
+  const float lse = d.scal[1];
+  return (int32_t)softmax_choice_terms(
+      d.x, d.n, [lse](float v) { return (double)np_expf(v - lse); }, d.csum, d.nblocks,
+      [&] { return d.uniforms ? d.uniforms[b] : philox_uniform(d.seed, *d.counter, b); });
 }
 
 // ---------------------------------------------------------------------------

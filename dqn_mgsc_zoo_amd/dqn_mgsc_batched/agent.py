@@ -99,10 +99,9 @@ class MGSCDqn(agent_base.DeviceDqnAgent):
     call: the replay Generator's uniforms are resolved into slots inside the
     learner's forward launch (Learner.step_logits)."""
     import torch  # pylint: disable=g-import-not-at-top
-    if getattr(self._replay, 'exact_sampling', False):
-      # the reference's own probabilities (dqz_logits_sample_exact), then the step
-      self._learner.step(self._store(), self._replay.sample_slots(self._batch_size))
-      return
+    # with exact_sampling the draw is the reference's own float32
+    # probabilities and choice (dqz_learner_step_logits_exact), same call shape
+    exact = bool(getattr(self._replay, 'exact_sampling', False))
     u = self._replay.draw_uniforms(self._batch_size)
     dev = self._learner.device
     if self._slots_cache is None:
@@ -111,7 +110,7 @@ class MGSCDqn(agent_base.DeviceDqnAgent):
     slots, u_dev = self._slots_cache
     self._uploader()(u_dev, np.asarray(u, np.float64))
     self._learner.step_logits(self._store(), self._replay.device_logits, slots,
-                              uniforms=u_dev)
+                              uniforms=u_dev, exact=exact)
 
   def _uploader(self):
     """Host -> device copies without a host wait (store.Uploader): the meta

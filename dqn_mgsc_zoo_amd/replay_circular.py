@@ -235,10 +235,10 @@ class CircularLogitBuffer:
   def __init__(self, capacity: int, random_state: np.random.Generator,
                device='cuda', exact_sampling=False):
     """exact_sampling: draw from the reference's own float32 probabilities
-    (dqz_logits_sample_exact: six passes over the buffer per draw) instead
-    of the running-state terms (O(1) per write, a float32 ulp per term), and
-    form default logits with its own logsumexp (dqz_logits_add_exact, four
-    passes per add)."""
+    (dqz_logits_sample_exact / dqz_learner_step_logits_exact: three passes
+    over the buffer per draw) instead of the running-state terms (O(1) per
+    write, a float32 ulp per term), and form default logits with its own
+    logsumexp (dqz_logits_add_exact, two passes per add)."""
     self._dev = _DeviceLogits(capacity, device)
     self._capacity = capacity
     self._size = 0

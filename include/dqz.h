@@ -160,6 +160,26 @@ int dqz_learner_step_logits(dqz_learner* learner, const dqz_params* params, cons
                             dqz_logit_buffer* buf, const float* logits, uint64_t seed, uint64_t* counter_dev,
                             const double* uniforms, int32_t* slots_out, void* stream);
 
+/* The same step with the reference's own draw, bit for bit: the exact mode
+ * of dqz_logits_sample_exact inside the forward launch.  Replaces
+ * `self._rng_state.choice(self._capacity, size=size, p=self.as_probs())` with
+ * p = probabilities_from_logits(logits) (replay_circular.py:69-76, 205-217,
+ * 540-545) and the learner update that follows it
+ * (dqn_mgsc_batched/agent.py:341-360).  Three preparation launches form c,
+ * the float32 logsumexp and the chunk sums of p = exp(x - lse) as numpy does;
+ * then each conv1 workgroup of sample b searches the CDF for uniforms[b]
+ * (device f64 [B], the replay Generator's random(B)) or for Philox uniform b
+ * of step *counter_dev, which then advances by one.  Exactly one of
+ * counter_dev / uniforms is given.  slots_out: device int32 [B].  Independent
+ * of the running log-sum-exp state; no host synchronisation, no allocation,
+ * capturable in a graph.  Calls that share one dqz_logit_buffer
+ * (dqz_logits_sample_exact and dqz_logits_add_exact included) must be ordered
+ * on one stream: they share its scratch. */
+int dqz_learner_step_logits_exact(dqz_learner* learner, const dqz_params* params, const dqz_store* store,
+                                  dqz_logit_buffer* buf, const float* logits, uint64_t seed,
+                                  uint64_t* counter_dev, const double* uniforms, int32_t* slots_out,
+                                  void* stream);
+
 /* Gradient only: d loss / d params of the same step into grad_out (device
  * f32, dqz_param_layout order, padding untouched); params->online / mu / nu
  * are not modified and mu / nu may be NULL.  = jax.grad(loss_fn) at
@@ -381,7 +401,9 @@ int dqz_logits_sample_slots(dqz_logit_buffer* buf, const float* logits, uint64_t
  * (replay_circular.py:205-217, :540-545): searchsorted(cumsum(p) / total, u,
  * 'right'), the cumsum in float64 in chunk order (a draw can differ from
  * numpy's sequential cumsum only for a uniform within float64 rounding of a
- * CDF step).  Six passes over the buffer; independent of the running state.
+ * CDF step).  Four launches (three preparation passes over the buffer, then
+ * the draws); independent of the running state.  Calls that share one
+ * dqz_logit_buffer must be ordered on one stream: they share its scratch.
  * n = 0: p_out only.  Replaces the reference's `self._rng_state.choice(
  * self._capacity, size=size, p=self.as_probs())` (replay_circular.py:208). */
 int dqz_logits_sample_exact(dqz_logit_buffer* buf, const float* logits, const double* uniforms, int n,
@@ -390,7 +412,8 @@ int dqz_logits_sample_exact(dqz_logit_buffer* buf, const float* logits, const do
  * add / replace): logits[clear_pos] = -inf first when clear_pos >= 0, then
  * logits[write_pos] = 0 for size 0, else float32(logsumexp(logits) -
  * log(size)) with numpy's float32 logsumexp (as dqz_logits_sample_exact forms
- * it) and a float64 log.  Five small launches, four passes over the buffer;
+ * it) and a float64 log.  Three small launches (four with a clear), two
+ * passes over the buffer;
  * the running state is left unknown (the next default-mode call re-seeds). */
 int dqz_logits_add_exact(dqz_logit_buffer* buf, float* logits, int64_t clear_pos, int64_t write_pos, int64_t size,
                          void* stream);

@@ -1,6 +1,7 @@
 """Full agent loop throughput: parts.run_loop over a synthetic Atari-like env.
 
 usage (GPU box): python tools/agent_loop_bench.py [--frames N] [--kind dqn|double|mgsc|mgsc_reservoir]
+                 [--exact-sampling]
 
 Drives the DQN agent as run_atari does: one agent.step per environment
 frame, the processor returning a stacked observation every 4th frame
@@ -58,20 +59,23 @@ class RepeatStacker(fake_env.FrameStacker):
     return super().__call__(timestep)
 
 
-def make_mgsc_agent(kind, capacity, seed=0, preprocessor=None, meta_batch=100):
+def make_mgsc_agent(kind, capacity, seed=0, preprocessor=None, meta_batch=100, exact_sampling=False):
   """dqn_mgsc_batched (FIFO logits, first-order meta-gradient) or
   dqn_mgsc_batched_reservoir (reservoir logits, second order), with the
   reference's training settings (run_mgscdqnbatched_normal.sh /
-  run_mgscdqnbatched_reservoir.sh: meta batch 100, learn period 16)."""
+  run_mgscdqnbatched_reservoir.sh: meta batch 100, learn period 16).
+  exact_sampling: the replay draws and adds with the reference's own float32
+  probabilities (replay_circular.py exact mode)."""
   from dqn_mgsc_zoo_amd import replay_circular as rc  # pylint: disable=g-import-not-at-top
   if kind == 'mgsc':
     from dqn_mgsc_zoo_amd.dqn_mgsc_batched import agent as agent_lib  # pylint: disable=g-import-not-at-top
     replay = rc.MGSCFiFoTransitionReplay(capacity, rc.Transition(None, None, None, None, None),
-                                         np.random.default_rng(seed))
+                                         np.random.default_rng(seed), exact_sampling=exact_sampling)
   else:
     from dqn_mgsc_zoo_amd.dqn_mgsc_batched_reservoir import agent as agent_lib  # pylint: disable=g-import-not-at-top
     replay = rc.MGSCReservoirTransitionReplay(capacity, rc.Transition(None, None, None, None, None),
-                                              np.random.default_rng(seed))
+                                              np.random.default_rng(seed),
+                                              exact_sampling=exact_sampling)
   return agent_lib.MGSCDqn(
       preprocessor=preprocessor or RepeatStacker(),
       sample_network_input=np.zeros((84, 84, 4), np.uint8),
@@ -86,9 +90,11 @@ def make_mgsc_agent(kind, capacity, seed=0, preprocessor=None, meta_batch=100):
       meta_optimizer=learner_lib.adam(2.5e-4), meta_batch_size=meta_batch)
 
 
-def make_agent(kind, capacity, seed=0, preprocessor=None):
+def make_agent(kind, capacity, seed=0, preprocessor=None, exact_sampling=False):
   if kind in ('mgsc', 'mgsc_reservoir'):
-    return make_mgsc_agent(kind, capacity, seed, preprocessor)
+    return make_mgsc_agent(kind, capacity, seed, preprocessor, exact_sampling=exact_sampling)
+  if exact_sampling:
+    raise ValueError('--exact-sampling applies to the learned-logit replays (mgsc, mgsc_reservoir)')
   rs = np.random.RandomState(seed)
   structure = replay_lib.Transition(None, None, None, None, None)
   if kind == 'double':
@@ -120,12 +126,15 @@ def main():
   ap.add_argument('--env', default='stacked', choices=['stacked', 'atari-device', 'atari-host'],
                   help='stacked: pre-stacked 84x84 frames; atari-*: raw RGB frames through '
                        'processors.atari with the observation math on device or on the host')
+  ap.add_argument('--exact-sampling', action='store_true',
+                  help='mgsc kinds: draw and add with the reference\'s own float32 probabilities '
+                       '(the learn step is then dqz_learner_step_logits_exact)')
   args = ap.parse_args()
   pre = None
   if args.env != 'stacked':
     from dqn_mgsc_zoo_amd import processors  # pylint: disable=g-import-not-at-top
     pre = processors.atari(observation_frame=host_atari_frame if args.env == 'atari-host' else None)
-  agent = make_agent(args.kind, args.capacity, preprocessor=pre)
+  agent = make_agent(args.kind, args.capacity, preprocessor=pre, exact_sampling=args.exact_sampling)
   times = {'act': 0.0, 'add': 0.0, 'learn': 0.0}
   counts = {'act': 0, 'add': 0, 'learn': 0}
   mgsc = args.kind.startswith('mgsc')
@@ -167,7 +176,8 @@ def main():
     next(loop)
   torch.cuda.synchronize()
   dt = time.perf_counter() - t0
-  out = {'kind': args.kind, 'env': args.env, 'frames': args.frames, 'seconds': round(dt, 3),
+  out = {'kind': args.kind, 'env': args.env, 'exact_sampling': bool(args.exact_sampling),
+         'frames': args.frames, 'seconds': round(dt, 3),
          'frames_per_s': round(args.frames / dt, 1),
          'learner_steps_per_s': round(counts['learn'] / dt, 1),
          'us_per_frame': round(1e6 * dt / args.frames, 1)}
