@@ -102,6 +102,38 @@ class DqzTransitionPut(ctypes.Structure):
   ]
 
 
+class DqzJumble(ctypes.Structure):
+  _fields_ = [
+      ('slot', ctypes.c_int64),
+      ('src_s_tm1', ctypes.c_int64),
+      ('src_action', ctypes.c_int64),
+      ('src_reward', ctypes.c_int64),
+      ('src_discount', ctypes.c_int64),
+      ('src_s_t', ctypes.c_int64),
+      ('frame_rows', ctypes.c_int32 * 8),
+      ('flags', ctypes.c_void_p),
+  ]
+
+
+class DqzCensusClass(ctypes.Structure):
+  _fields_ = [
+      ('max_seen', ctypes.c_float),
+      ('min_seen', ctypes.c_float),
+      ('probe_sum', ctypes.c_double * 5),
+      ('probe_num', ctypes.c_int64 * 5),
+      ('count', ctypes.c_int64),
+      ('mass', ctypes.c_double),
+  ]
+
+
+class DqzCensus(ctypes.Structure):
+  """dqz_census: cls[0] real, cls[1] nonsense; probes in CENSUS_PROBES order."""
+  _fields_ = [('cls', DqzCensusClass * 2), ('calls', ctypes.c_int64)]
+
+
+CENSUS_PROBES = ('entry', '1st_quarter', '2nd_quarter', '3rd_quarter', 'exit')
+
+
 class DqzPerDraw(ctypes.Structure):
   _fields_ = [
       ('tree', ctypes.c_void_p),
@@ -191,6 +223,9 @@ SIGNATURES = {
     'dqz_store_put': (
         _int, [ctypes.POINTER(DqzStore), ctypes.POINTER(DqzTransitionPut), _vp,
                _vp]),
+    'dqz_store_jumble': (
+        _int, [ctypes.POINTER(DqzStore), ctypes.POINTER(DqzJumble), _vp]),
+    'dqz_logits_census': (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     'dqz_frame_plan_create': (_int, [_int, _int, _int, _int, ctypes.POINTER(_vp)]),
     'dqz_frame_plan_destroy': (_int, [_vp]),
     'dqz_atari_frame': (_int, [_vp, _vp, _int, _vp, _vp]),

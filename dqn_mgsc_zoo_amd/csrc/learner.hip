@@ -17,6 +17,7 @@
 #include "meta.hpp"
 #include "hvp.hpp"
 #include "preprocess.hpp"
+#include "census.hpp"
 
 using namespace dqz;
 
@@ -61,6 +62,28 @@ int dqz_store_put(const dqz_store* S, const dqz_transition_put* t, const uint8_t
                      (hipStream_t)stream, const_cast<uint8_t*>(S->frames), const_cast<int32_t*>(S->fidx),
                      const_cast<int32_t*>(S->action), const_cast<float*>(S->reward),
                      const_cast<float*>(S->discount), *t, static_cast<const uint8_t*>(dframes));
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+int dqz_store_jumble(const dqz_store* S, const dqz_jumble* j, void* stream) {
+  if (int rc = check_store(S)) return rc;
+  if (!j) return fail(DQZ_ERR_INVALID, "null jumble");
+  const int64_t slots[6] = {j->slot, j->src_s_tm1, j->src_action, j->src_reward, j->src_discount, j->src_s_t};
+  for (int i = 0; i < 6; ++i)
+    if (slots[i] < 0 || slots[i] >= S->capacity)
+      return fail(DQZ_ERR_INVALID, "jumble slot %lld out of range [0, %lld)", (long long)slots[i],
+                  (long long)S->capacity);
+  for (int i = 0; i < 8; ++i) {
+    if (j->frame_rows[i] < 0 || j->frame_rows[i] >= S->num_frames)
+      return fail(DQZ_ERR_INVALID, "frame_rows[%d] out of range", i);
+    for (int k = 0; k < i; ++k)
+      if (j->frame_rows[k] == j->frame_rows[i])
+        return fail(DQZ_ERR_INVALID, "frame_rows[%d] repeats frame_rows[%d]", i, k);
+  }
+  hipLaunchKernelGGL(store_jumble_kernel, dim3(8), dim3(256), 0, (hipStream_t)stream, const_cast<uint8_t*>(S->frames),
+                     const_cast<int32_t*>(S->fidx), const_cast<int32_t*>(S->action), const_cast<float*>(S->reward),
+                     const_cast<float*>(S->discount), *j);
   DQZ_HIP(hipGetLastError());
   return DQZ_OK;
 }
@@ -114,6 +137,7 @@ struct dqz_logit_buffer {
   int *prog_full, *prog_last;  // npx_program of a full and of the last buffer
   bool run_known;  // host side: every write since the last scan went through the library
   int run_adds;    // running adds since the last scan
+  void* census;    // dqz_logits_census: CensusScan[nblocks] | CensusMass[nblocks], allocated by its first call
 };
 
 // numpy's pairwise-summation recursion over one buffer of length L
@@ -226,6 +250,7 @@ int dqz_logit_buffer_create(int64_t capacity, int max_queries, dqz_logit_buffer*
 int dqz_logit_buffer_destroy(dqz_logit_buffer* b) {
   if (!b) return DQZ_OK;
   if (b->block) (void)hipFree(b->block);
+  if (b->census) (void)hipFree(b->census);
   delete b;
   return DQZ_OK;
 }
@@ -437,6 +462,33 @@ int dqz_logits_probs(dqz_logit_buffer* b, const float* logits, float* p_out, flo
   if (int rc = ensure_run(b, logits, st)) return rc;
   hipLaunchKernelGGL(logit_terms_kernel, dim3(b->nblocks), dim3(SM_THREADS), 0, st, logits, b->capacity, b->run,
                      b->csum, b->nblocks, p_out, (float*)nullptr, lse_out, (float*)nullptr);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+int dqz_logits_census(dqz_logit_buffer* b, const float* logits, const uint8_t* flags, int64_t left_head, int64_t size,
+                      dqz_census* acc_dev, void* stream) {
+  if (!b || !logits || !flags || !acc_dev) return fail(DQZ_ERR_INVALID, "null argument");
+  if (left_head < 0 || left_head >= b->capacity)
+    return fail(DQZ_ERR_INVALID, "left_head %lld out of range [0, %lld)", (long long)left_head, (long long)b->capacity);
+  if (size < 0 || size > b->capacity)
+    return fail(DQZ_ERR_INVALID, "size %lld out of range [0, %lld]", (long long)size, (long long)b->capacity);
+  if (!b->census)
+    DQZ_HIP(hipMalloc(&b->census, (size_t)b->nblocks * (sizeof(CensusScan) + sizeof(CensusMass))));
+  hipStream_t st = (hipStream_t)stream;
+  CensusScan* scan = (CensusScan*)b->census;
+  CensusMass* mass = (CensusMass*)(scan + b->nblocks);
+  const int nparts = (int)((size + SM_CHUNK - 1) / SM_CHUNK);  // <= nblocks
+  if (nparts > 0) {
+    hipLaunchKernelGGL(census_scan_kernel, dim3(nparts), dim3(SM_THREADS), 0, st, logits, flags, b->capacity, left_head,
+                       size, scan);
+    DQZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(census_mass_kernel, dim3(nparts), dim3(SM_THREADS), 0, st, logits, flags, b->capacity, left_head,
+                       size, scan, nparts, mass);
+    DQZ_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(census_final_kernel, dim3(1), dim3(SM_THREADS), 0, st, logits, flags, b->capacity, left_head, size,
+                     scan, mass, nparts, acc_dev);
   DQZ_HIP(hipGetLastError());
   return DQZ_OK;
 }

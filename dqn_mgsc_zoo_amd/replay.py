@@ -228,12 +228,15 @@ class _DeviceStorage:
 
   def get_state(self):
     st = self.store
-    return {'kind': 'device', 'args': dict(self._args),
-            'frames': st.frames.cpu().numpy(), 'fidx': st.fidx.cpu().numpy(),
-            'action': st.action.cpu().numpy(),
-            'reward': st.reward.cpu().numpy(),
-            'discount': st.discount.cpu().numpy(),
-            'allocator': self.allocator.get_state()}
+    state = {'kind': 'device', 'args': dict(self._args),
+             'frames': st.frames.cpu().numpy(), 'fidx': st.fidx.cpu().numpy(),
+             'action': st.action.cpu().numpy(),
+             'reward': st.reward.cpu().numpy(),
+             'discount': st.discount.cpu().numpy(),
+             'allocator': self.allocator.get_state()}
+    if st.has_flags:  # only a store that composed transitions (FrameStore.jumble) has them
+      state['flags'] = st.flags.cpu().numpy()
+    return state
 
   def set_state(self, state):
     st = self.store
@@ -243,6 +246,10 @@ class _DeviceStorage:
     st.action.copy_(t.from_numpy(state['action']))
     st.reward.copy_(t.from_numpy(state['reward']))
     st.discount.copy_(t.from_numpy(state['discount']))
+    if 'flags' in state:
+      st.flags.copy_(t.from_numpy(state['flags']))
+    elif st.has_flags:  # an absent key means all zero
+      st.flags.zero_()
     self.allocator.set_state(state['allocator'])
 
 

@@ -84,6 +84,7 @@ class FrameStore:
                                 device=self.device)
     self._stage = None  # pinned staging slots of put(), allocated on first use
     self._stage_k = 0
+    self._flags = None  # uint8 [capacity], 1 = composed by jumble(); created on first use
     self._c = _native.DqzStore(
         self.frames.data_ptr(), self.fidx.data_ptr(), self.action.data_ptr(),
         self.reward.data_ptr(), self.discount.data_ptr(), self.capacity,
@@ -129,6 +130,39 @@ class FrameStore:
     if self._stage_ev[k] is None:
       self._stage_ev[k] = torch.cuda.Event()
     self._stage_ev[k].record()
+
+  @property
+  def flags(self):
+    """Device uint8 [capacity]: 1 where the slot holds a transition composed
+    by jumble() (the nonsense class of dqz_logits_census), else 0."""
+    if self._flags is None:
+      self._flags = torch.zeros((self.capacity,), dtype=torch.uint8, device=self.device)
+    return self._flags
+
+  @property
+  def has_flags(self):
+    return self._flags is not None
+
+  def set_flag(self, slot, value):
+    """flags[slot] = value (one small fill; a slot reused by a real add)."""
+    self.flags[int(slot):int(slot) + 1].fill_(int(value))
+
+  def jumble(self, slot, s_tm1_from, a_tm1_from, r_t_from, discount_t_from, s_t_from, frame_rows):
+    """One replay add composed from stored slots, device to device in one
+    launch (dqz_store_jumble): the stacks of `s_tm1_from` / `s_t_from` are
+    copied into the eight fresh pool rows `frame_rows`, the scalars come from
+    the other three slots, and flags[slot] becomes 1."""
+    j = _native.DqzJumble()
+    j.slot = int(slot)
+    j.src_s_tm1, j.src_action, j.src_reward = int(s_tm1_from), int(a_tm1_from), int(r_t_from)
+    j.src_discount, j.src_s_t = int(discount_t_from), int(s_t_from)
+    if len(frame_rows) != 8:
+      raise ValueError('jumble needs 8 reserved pool rows, got %d' % len(frame_rows))
+    for i, row in enumerate(frame_rows):
+      j.frame_rows[i] = int(row)
+    j.flags = self.flags.data_ptr()
+    _native.check(_native.lib().dqz_store_jumble(self.c_ref(), ctypes.byref(j),
+                                                 _native.stream_handle()))
 
   def gather_stacks(self, slots, which, stream=None):
     """uint8 [n,84,84,4] stacks of `which` (0 = s_tm1, 1 = s_t) on device."""
@@ -224,7 +258,9 @@ class FrameAllocator:
       self._recent.popitem(last=False)
     return pos
 
-  def _append(self, ch, oldest_live_slot):
+  def _claim(self, oldest_live_slot):
+    """The next absolute ring position, once nothing live references the
+    frame it overwrites."""
     pos = self._pos
     victim = pos - self._store.num_frames
     if victim >= 0 and oldest_live_slot is not None:
@@ -233,9 +269,32 @@ class FrameAllocator:
             'Frame pool of %d frames is too small for this transition stream: '
             'overwriting frame %d still referenced by a live transition. '
             'Increase num_frames.' % (self._store.num_frames, victim))
-    self._new.append((pos % self._store.num_frames, ch))
     self._pos += 1
     return pos
+
+  def _append(self, ch, oldest_live_slot):
+    pos = self._claim(oldest_live_slot)
+    self._new.append((pos % self._store.num_frames, ch))
+    return pos
+
+  def reserve(self, slot, n, oldest_live_slot=None):
+    """Ring mode: n fresh absolute positions for frames that `slot` will own
+    and that are written on device (FrameStore.jumble), under the overwrite
+    check of a host-written frame.  `oldest_live_slot` is the oldest live
+    transition while the sources are read, i.e. before the add pops anything:
+    it is itself a source, so no reserved row may be one of its rows.  The
+    reserved frames are not fingerprinted: they enter neither the window of
+    recent frames nor the s_t hand-back."""
+    if self._mode != 'ring':
+      raise ValueError('reserve() is for the frame ring of FIFO replays')
+    start = self._pos
+    try:
+      out = [self._claim(oldest_live_slot) for _ in range(n)]
+    except RuntimeError:
+      self._pos = start  # nothing was written: give the claimed rows back
+      raise
+    self._min_ref[slot] = out[0] if out else self._pos
+    return out
 
   def _allocate_slot(self, slot, s_tm1, s_t):
     base = slot * self._per_slot

@@ -304,6 +304,31 @@ typedef struct dqz_transition_put {
 int dqz_store_put(const dqz_store* store, const dqz_transition_put* t, const uint8_t* frames,
                   void* stream);
 
+/* One replay add composed from stored transitions, device to device, in one
+ * launch (the jumbled transition of
+ * dqn_mgsc_batched_nonsense_transitions/agent.py:277-286: s_tm1, a_tm1, r_t,
+ * discount_t and s_t each taken from another stored item).  For channel c in
+ * 0..3 the source pool row is fidx[src_s_tm1][c], for c in 4..7 it is
+ * fidx[src_s_t][c]; a source row >= 0 is copied (7,056 bytes) into pool row
+ * frame_rows[c] and fidx[slot][c] = frame_rows[c]; a source row of -1 (zero
+ * padding) gives fidx[slot][c] = -1 and leaves frame_rows[c] unused.
+ * action[slot] = action[src_action], reward[slot] = reward[src_reward],
+ * discount[slot] = discount[src_discount]; flags[slot] = 1 when `flags`
+ * (device uint8 [capacity]) is given.  The copies are needed because a FIFO
+ * frame ring recycles the sources' rows long before the composed item leaves
+ * the replay.  `slot` may equal any source (on a full ring it is the s_tm1
+ * source): every workgroup reads and writes only its own channel's fidx
+ * entry.  frame_rows must be fresh rows: pairwise distinct and none of them a
+ * row the sources reference (the allocator's job, store.FrameAllocator.reserve).
+ * Writes through the store's (caller-owned, writable) buffers. */
+typedef struct dqz_jumble {
+  int64_t slot;
+  int64_t src_s_tm1, src_action, src_reward, src_discount, src_s_t;
+  int32_t frame_rows[8];
+  uint8_t* flags;
+} dqz_jumble;
+int dqz_store_jumble(const dqz_store* store, const dqz_jumble* j, void* stream);
+
 /* Uniform sampling with replacement over live transitions, on device
  * (UniformDistribution.sample, replay.py:119-125; replay_circular.py:283-289).
  * Live slots are (base + j) mod capacity for j in [0, size).  FIFO replay:
@@ -427,6 +452,45 @@ int dqz_logits_probs(dqz_logit_buffer* buf, const float* logits, float* p_out, f
  * f32 exp between numpy and the device. */
 int dqz_logits_terms(dqz_logit_buffer* buf, const float* logits, float* t_out, double* csum_out, float* c_out,
                      void* stream);
+
+/* Census of the learned logits by class of transition: one pass of the
+ * per-timestep walk of dqn_mgsc_batched_nonsense_transitions/agent.py:290-310
+ * over the live window (left_head + i) mod capacity, i < size, on device.
+ * flags: device uint8 [capacity], class 1 (nonsense) where non-zero, class 0
+ * (real) otherwise (dqz_store_jumble sets them).  acc_dev: a dqz_census in
+ * device memory owned by the caller, who initialises it (max_seen = -inf,
+ * min_seen = +inf, the rest 0).  Per class:
+ *   max_seen / min_seen  over the live logits of every call so far;
+ *   probe_sum / probe_num  the logit at five positions of the window, added
+ *     once per call to the class of the slot found there: [0] entry
+ *     (i = size - 1), [1] 1st_quarter (3 (size / 4)), [2] 2nd_quarter
+ *     (size / 2), [3] 3rd_quarter (size / 4), [4] exit (0).  A position that
+ *     matches several probes counts once, for the first of exit, 3rd, 2nd,
+ *     1st, entry (the reference's elif chain).  Sums are float64, one add
+ *     per call (the reference accumulates in float32);
+ *   count  live slots of the class, this call;
+ *   mass   the class's share of the sampling probability, this call:
+ *     sum_class exp((double)x - (double)m) / sum_all, m the largest live
+ *     logit (0 when nothing is live).
+ * calls advances by one.  size == 0: counts and masses become 0, the running
+ * fields stay.  Slots outside the window are ignored whatever they hold.
+ * Three small launches, no float atomics (every sum has a fixed order: equal
+ * inputs give equal bits), no host synchronisation; the partials live in
+ * scratch of `buf`, allocated by the first call.  Calls that share one
+ * dqz_logit_buffer must be ordered on one stream. */
+typedef struct dqz_census_class {
+  float max_seen, min_seen;
+  double probe_sum[5];
+  int64_t probe_num[5];
+  int64_t count;
+  double mass;
+} dqz_census_class;
+typedef struct dqz_census {
+  dqz_census_class cls[2]; /* 0 real, 1 nonsense */
+  int64_t calls;
+} dqz_census;
+int dqz_logits_census(dqz_logit_buffer* buf, const float* logits, const uint8_t* flags, int64_t left_head,
+                      int64_t size, dqz_census* acc_dev, void* stream);
 
 /* n uniform doubles in [0,1) from Philox4x32-10 (counter advanced on device). */
 int dqz_uniform_philox(uint64_t seed, uint64_t* counter_dev, int n, double* out, void* stream);

@@ -1,6 +1,6 @@
 """Full agent loop throughput: parts.run_loop over a synthetic Atari-like env.
 
-usage (GPU box): python tools/agent_loop_bench.py [--frames N] [--kind dqn|double|mgsc|mgsc_reservoir]
+usage (GPU box): python tools/agent_loop_bench.py [--frames N] [--kind dqn|double|mgsc|mgsc_reservoir|mgsc_nonsense]
                  [--exact-sampling]
 
 Drives the DQN agent as run_atari does: one agent.step per environment
@@ -67,7 +67,14 @@ def make_mgsc_agent(kind, capacity, seed=0, preprocessor=None, meta_batch=100, e
   exact_sampling: the replay draws and adds with the reference's own float32
   probabilities (replay_circular.py exact mode)."""
   from dqn_mgsc_zoo_amd import replay_circular as rc  # pylint: disable=g-import-not-at-top
-  if kind == 'mgsc':
+  extra = {}
+  if kind == 'mgsc_nonsense':  # dqn_mgsc_batched_nonsense_transitions, ratio 50 (its run_atari.py:102)
+    from dqn_mgsc_zoo_amd import replay_circular_nonsense as rcn  # pylint: disable=g-import-not-at-top
+    from dqn_mgsc_zoo_amd.dqn_mgsc_batched_nonsense_transitions import agent as agent_lib  # pylint: disable=g-import-not-at-top
+    replay = rcn.MGSCFiFoTransitionReplay(capacity, rc.Transition(None, None, None, None, None),
+                                          np.random.default_rng(seed), exact_sampling=exact_sampling)
+    extra = {'nonsense_transition_ratio': 50}
+  elif kind == 'mgsc':
     from dqn_mgsc_zoo_amd.dqn_mgsc_batched import agent as agent_lib  # pylint: disable=g-import-not-at-top
     replay = rc.MGSCFiFoTransitionReplay(capacity, rc.Transition(None, None, None, None, None),
                                          np.random.default_rng(seed), exact_sampling=exact_sampling)
@@ -87,11 +94,11 @@ def make_mgsc_agent(kind, capacity, seed=0, preprocessor=None, meta_batch=100, e
       min_replay_capacity_fraction=0.05, learn_period=16,
       target_network_update_period=40_000, grad_error_bound=1.0 / 32,
       rng_key=np.array([0, seed], np.uint32),
-      meta_optimizer=learner_lib.adam(2.5e-4), meta_batch_size=meta_batch)
+      meta_optimizer=learner_lib.adam(2.5e-4), meta_batch_size=meta_batch, **extra)
 
 
 def make_agent(kind, capacity, seed=0, preprocessor=None, exact_sampling=False):
-  if kind in ('mgsc', 'mgsc_reservoir'):
+  if kind.startswith('mgsc'):
     return make_mgsc_agent(kind, capacity, seed, preprocessor, exact_sampling=exact_sampling)
   if exact_sampling:
     raise ValueError('--exact-sampling applies to the learned-logit replays (mgsc, mgsc_reservoir)')
@@ -122,7 +129,7 @@ def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--frames', type=int, default=8000)
   ap.add_argument('--capacity', type=int, default=20_000)
-  ap.add_argument('--kind', default='dqn', choices=['dqn', 'double', 'mgsc', 'mgsc_reservoir'])
+  ap.add_argument('--kind', default='dqn', choices=['dqn', 'double', 'mgsc', 'mgsc_reservoir', 'mgsc_nonsense'])
   ap.add_argument('--env', default='stacked', choices=['stacked', 'atari-device', 'atari-host'],
                   help='stacked: pre-stacked 84x84 frames; atari-*: raw RGB frames through '
                        'processors.atari with the observation math on device or on the host')
@@ -156,6 +163,10 @@ def main():
   if mgsc:  # these agents add through the replay directly (agent.py:268-270)
     agent._meta_prioritization_learn = wrap('meta', agent._meta_prioritization_learn)  # pylint: disable=protected-access
     agent._replay.add = wrap('add', agent._replay.add)  # pylint: disable=protected-access
+    if args.kind == 'mgsc_nonsense':
+      for name, attr in (('add_jumbled', 'add_jumbled'), ('census', 'census')):
+        times[name], counts[name] = 0.0, 0
+        setattr(agent._replay, attr, wrap(name, getattr(agent._replay, attr)))  # pylint: disable=protected-access
     # the meta step's host pieces (inside 'meta')
     for name, obj, attr in (('meta_batch', agent._replay, 'meta_batch_slots'),  # pylint: disable=protected-access
                             ('meta_online', agent.meta_learner, 'set_online_transition'),
