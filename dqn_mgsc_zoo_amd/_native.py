@@ -86,6 +86,24 @@ class DqzMetaConfig(ctypes.Structure):
   ]
 
 
+OPT_ADAM = 0
+OPT_RMSPROP = 1
+
+
+class DqzOptimizerConfig(ctypes.Structure):
+  _fields_ = [
+      ('kind', ctypes.c_int),
+      ('learning_rate', ctypes.c_float),
+      ('b1', ctypes.c_float),
+      ('b2', ctypes.c_float),
+      ('decay', ctypes.c_float),
+      ('eps', ctypes.c_float),
+      ('max_global_grad_norm', ctypes.c_float),
+      ('num_actions', ctypes.c_int),
+      ('shared_bias', ctypes.c_int),
+  ]
+
+
 class DqzAction(ctypes.Structure):
   _fields_ = [('action', ctypes.c_int32), ('value', ctypes.c_float)]
 
@@ -199,6 +217,23 @@ SIGNATURES = {
         _int,
         [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore),
          ctypes.POINTER(DqzPerDraw), _vp]),
+    'dqz_optimizer_create': (
+        _int, [ctypes.POINTER(DqzOptimizerConfig), ctypes.POINTER(_vp)]),
+    'dqz_optimizer_destroy': (_int, [_vp]),
+    'dqz_optimizer_apply': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dqz_optimizer_outputs': (_int, [_vp, _vp, _vp]),
+    'dqz_learner_step_opt': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
+         _vp, _vp, _vp]),
+    'dqz_learner_step_opt_uniform': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _i64, _i64,
+         _i64, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    'dqz_learner_step_opt_per_draw': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore),
+         ctypes.POINTER(DqzPerDraw), _vp, _vp, _vp]),
     'dqz_learner_grad': (
         _int,
         [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,

@@ -189,8 +189,7 @@ class DeviceDqnAgent(parts.Agent):
     return {
         'rng_key': optim_state.pack_key(self._act_seed, self._act_count),
         'frame_t': self._frame_t,
-        'opt_state': optim_state.rmsprop_state(lrn.params_tree('mu'),
-                                               lrn.params_tree('nu')),
+        'opt_state': lrn.opt_state(),
         'online_params': lrn.params_tree('online'),
         'target_params': lrn.params_tree('target'),
         'replay': self._replay.get_state(),
@@ -200,7 +199,7 @@ class DeviceDqnAgent(parts.Agent):
     self._act_seed, self._act_count = optim_state.unpack_key(state['rng_key'])
     self._frame_t = state['frame_t']
     self._learner.set_params(state['online_params'], state['target_params'])
-    self._learner.set_opt_state(*optim_state.rmsprop_moments(state['opt_state']))
+    self._learner.load_opt_state(state['opt_state'])
     self._replay.set_state(state['replay'])
 
   def _store(self):

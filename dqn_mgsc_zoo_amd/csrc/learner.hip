@@ -2,7 +2,9 @@
 // are learner_step.hip's code object; common.hpp, "Two translation units"):
 // the replay-side device code (frame store puts and gathers, the uniform,
 // learned-logit and prioritized samplers, sum trees), the MGSC meta-update
-// and its HVP, Atari preprocessing, and the C-ABI entries that drive them.
+// and its HVP, Atari preprocessing, the optimizers applied to a finished
+// gradient (Adam, plain RMSProp, global-norm clipping), and the C-ABI entries
+// that drive them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +20,7 @@
 #include "hvp.hpp"
 #include "preprocess.hpp"
 #include "census.hpp"
+#include "optim.hpp"
 
 using namespace dqz;
 
@@ -630,8 +633,10 @@ int dqz_per_sample(const double* tree, int64_t cap, int64_t live_base, int64_t s
   return DQZ_OK;
 }
 
-int dqz_learner_step_per_draw(dqz_learner* L, const dqz_params* P, const dqz_store* S, const dqz_per_draw* d,
-                              void* stream) {
+// dqz_learner_step_per_draw, or with gout the same step in gradient mode
+// (dqz_learner_step_opt_per_draw)
+static int per_draw_step(dqz_learner* L, const dqz_params* P, const dqz_store* S, const dqz_per_draw* d, float* gout,
+                         void* stream) {
   if (!L || !d || !d->tree || !d->out_indices || !d->out_slots || !d->out_probs || !d->max_seen_dev)
     return fail(DQZ_ERR_INVALID, "null argument");
   if (L->cfg.algo != DQZ_ALGO_PER) return fail(DQZ_ERR_INVALID, "the learner is not a PER learner");
@@ -667,8 +672,168 @@ int dqz_learner_step_per_draw(dqz_learner* L, const dqz_params* P, const dqz_sto
   a.out_weights = d->out_weights;
   a.out_probs = d->out_probs;
   PerWbArgs wb{d->tree, d->cap, levels, d->out_indices, nullptr, d->alpha, 0, d->max_seen_dev};
-  return step_impl(L, P, S, d->out_slots, nullptr, stream, kNoProfile, nullptr, nullptr, nullptr, 0, 0, &wb, nullptr,
+  return step_impl(L, P, S, d->out_slots, nullptr, stream, kNoProfile, gout, nullptr, nullptr, 0, 0, &wb, nullptr,
                    &a);
+}
+
+int dqz_learner_step_per_draw(dqz_learner* L, const dqz_params* P, const dqz_store* S, const dqz_per_draw* d,
+                              void* stream) {
+  return per_draw_step(L, P, S, d, nullptr, stream);
+}
+
+// ---------------------------------------------------------------------------
+// optimizers on a finished gradient (optim.hpp)
+
+struct dqz_optimizer {
+  dqz_optimizer_config cfg;
+  int64_t total;
+  OptLeaves lv;
+  int nblocks;        // workgroups of the apply launch
+  int nparts;         // workgroups of the norm launch = its partials
+  float* grad;        // [total] the steps' gradient; padding zero since creation
+  double* part;       // [nparts] sums of squares of the last gradient normed
+  const float* last;  // the most recent apply's gradient (dqz_optimizer_outputs without clipping)
+  void* block;
+};
+
+int dqz_optimizer_create(const dqz_optimizer_config* cfg, dqz_optimizer** out) {
+  if (!cfg || !out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (cfg->kind != DQZ_OPT_ADAM && cfg->kind != DQZ_OPT_RMSPROP)
+    return fail(DQZ_ERR_INVALID, "optimizer kind must be DQZ_OPT_ADAM or DQZ_OPT_RMSPROP");
+  if (cfg->num_actions < 1 || cfg->num_actions > MAXA) return fail(DQZ_ERR_INVALID, "num_actions must be in [1, %d]", MAXA);
+  if (!(cfg->eps >= 0.f)) return fail(DQZ_ERR_INVALID, "eps must be >= 0");
+  if (cfg->kind == DQZ_OPT_ADAM && !(cfg->b1 >= 0.f && cfg->b1 < 1.f && cfg->b2 >= 0.f && cfg->b2 < 1.f))
+    return fail(DQZ_ERR_INVALID, "b1 and b2 must be in [0, 1)");
+  if (cfg->kind == DQZ_OPT_RMSPROP && !(cfg->decay >= 0.f && cfg->decay <= 1.f))
+    return fail(DQZ_ERR_INVALID, "decay must be in [0, 1]");
+  dqz_optimizer* o = new dqz_optimizer();
+  o->cfg = *cfg;
+  int64_t off[10], sz[10];
+  param_layout(cfg->num_actions, cfg->shared_bias, off, sz, &o->total);
+  for (int i = 0; i < 10; ++i) {
+    o->lv.off4[i] = off[i] / 4;
+    o->lv.end[i] = off[i] + sz[i];
+  }
+  o->lv.n4 = o->total / 4;
+  o->nblocks = (int)((o->lv.n4 + OPT_THREADS * OPT_UNROLL - 1) / (OPT_THREADS * OPT_UNROLL));
+  o->nparts = (int)((o->lv.n4 + OPT_THREADS * OPT_NORM_UNROLL - 1) / (OPT_THREADS * OPT_NORM_UNROLL));
+  const size_t grad_b = (size_t)o->total * sizeof(float);  // a multiple of 256
+  const size_t bytes = grad_b + (size_t)o->nparts * sizeof(double);
+  if (hipMalloc(&o->block, bytes) != hipSuccess || hipMemset(o->block, 0, bytes) != hipSuccess) {
+    if (o->block) (void)hipFree(o->block);
+    delete o;
+    return fail(DQZ_ERR_HIP, "hipMalloc of %lld bytes of optimizer scratch failed", (long long)bytes);
+  }
+  o->grad = (float*)o->block;
+  o->part = (double*)((char*)o->block + grad_b);
+  o->last = nullptr;
+  *out = o;
+  return DQZ_OK;
+}
+
+int dqz_optimizer_destroy(dqz_optimizer* o) {
+  if (!o) return DQZ_OK;
+  if (o->block) (void)hipFree(o->block);
+  delete o;
+  return DQZ_OK;
+}
+
+static int opt_norm(dqz_optimizer* o, const float* grad, hipStream_t st) {
+  hipLaunchKernelGGL(opt_norm_kernel, dim3(o->nparts), dim3(OPT_THREADS), 0, st, (const float4*)grad, o->lv, o->part);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+int dqz_optimizer_apply(dqz_optimizer* o, float* th, const float* grad, float* mu, float* nu, int32_t* count,
+                        void* stream) {
+  if (!o || !th || !grad || !nu) return fail(DQZ_ERR_INVALID, "null argument");
+  const bool is_adam = o->cfg.kind == DQZ_OPT_ADAM;
+  if (is_adam && (!mu || !count)) return fail(DQZ_ERR_INVALID, "Adam needs mu and count");
+  if ((reinterpret_cast<uintptr_t>(th) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(nu) |
+       reinterpret_cast<uintptr_t>(mu)) % 16)
+    return fail(DQZ_ERR_INVALID, "parameters, gradient and moments must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const bool clip = o->cfg.max_global_grad_norm > 0.f;
+  if (clip)
+    if (int rc = opt_norm(o, grad, st)) return rc;
+  OptArgs a{};
+  a.th = (float4*)th;
+  a.m = (float4*)mu;
+  a.v = (float4*)nu;
+  a.g = (const float4*)grad;
+  a.lv = o->lv;
+  a.kind = o->cfg.kind;
+  a.lr = o->cfg.learning_rate;
+  a.b1 = o->cfg.b1;
+  a.b2 = o->cfg.b2;
+  a.decay = o->cfg.decay;
+  a.eps = o->cfg.eps;
+  a.clip = o->cfg.max_global_grad_norm;
+  a.part = clip ? o->part : nullptr;
+  a.nparts = o->nparts;
+  a.count = count;
+  if (is_adam) {
+    hipLaunchKernelGGL(opt_adam_kernel, dim3(o->nblocks), dim3(OPT_THREADS), 0, st, a);
+    DQZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(opt_count_kernel, dim3(1), dim3(64), 0, st, count);
+  } else {
+    hipLaunchKernelGGL(opt_rms_kernel, dim3(o->nblocks), dim3(OPT_THREADS), 0, st, a);
+  }
+  DQZ_HIP(hipGetLastError());
+  o->last = grad;
+  return DQZ_OK;
+}
+
+int dqz_optimizer_outputs(dqz_optimizer* o, float* gnorm, void* stream) {
+  if (!o || !gnorm) return fail(DQZ_ERR_INVALID, "null argument");
+  if (!o->last) return fail(DQZ_ERR_INVALID, "no step or apply has run on this optimizer");
+  hipStream_t st = (hipStream_t)stream;
+  if (!(o->cfg.max_global_grad_norm > 0.f))
+    if (int rc = opt_norm(o, o->last, st)) return rc;
+  hipLaunchKernelGGL(opt_norm_out_kernel, dim3(1), dim3(OPT_THREADS), 0, st, o->part, o->nparts, gnorm);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+// what a step in gradient mode followed by dqz_optimizer_apply needs checked
+// before anything is enqueued
+static int check_step_opt(const dqz_learner* L, const dqz_params* P, const dqz_optimizer* o, const int32_t* count) {
+  if (!L || !P || !o) return fail(DQZ_ERR_INVALID, "null argument");
+  if (!P->online || !P->nu) return fail(DQZ_ERR_INVALID, "null optimizer state");
+  if (o->cfg.kind == DQZ_OPT_ADAM && (!P->mu || !count)) return fail(DQZ_ERR_INVALID, "Adam needs mu and count");
+  if ((reinterpret_cast<uintptr_t>(P->online) | reinterpret_cast<uintptr_t>(P->nu) |
+       reinterpret_cast<uintptr_t>(P->mu)) % 16)
+    return fail(DQZ_ERR_INVALID, "parameters and moments must be 16-byte aligned");
+  if (o->cfg.num_actions != L->cfg.num_actions || (o->cfg.shared_bias != 0) != (L->shared_bias != 0))
+    return fail(DQZ_ERR_INVALID, "the optimizer was created for another parameter layout");
+  return DQZ_OK;
+}
+
+int dqz_learner_step_opt(dqz_learner* L, const dqz_params* P, const dqz_store* S, const int32_t* slots,
+                         const float* is_weights, dqz_optimizer* o, int32_t* count, void* stream) {
+  if (int rc = check_step_opt(L, P, o, count)) return rc;
+  if (int rc = step_impl(L, P, S, slots, is_weights, stream, kNoProfile, o->grad)) return rc;
+  return dqz_optimizer_apply(o, P->online, o->grad, P->mu, P->nu, count, stream);
+}
+
+int dqz_learner_step_opt_uniform(dqz_learner* L, const dqz_params* P, const dqz_store* S, int64_t base, int64_t size,
+                                 int64_t capacity, uint64_t seed, uint64_t* counter_dev, int32_t* slots_out,
+                                 dqz_optimizer* o, int32_t* count, void* stream) {
+  if (int rc = check_step_opt(L, P, o, count)) return rc;
+  if (!counter_dev || !slots_out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (size < 1) return fail(DQZ_ERR_INVALID, "cannot sample from an empty replay (size=%lld)", (long long)size);
+  if (capacity < size || base < 0) return fail(DQZ_ERR_INVALID, "bad replay geometry");
+  if (L->cfg.algo == DQZ_ALGO_PER) return fail(DQZ_ERR_INVALID, "PER samples by priority, not uniformly");
+  const UniformDraw d{base % capacity, size, capacity, seed, counter_dev, slots_out};
+  if (int rc = step_impl(L, P, S, slots_out, nullptr, stream, kNoProfile, o->grad, nullptr, &d)) return rc;
+  return dqz_optimizer_apply(o, P->online, o->grad, P->mu, P->nu, count, stream);
+}
+
+int dqz_learner_step_opt_per_draw(dqz_learner* L, const dqz_params* P, const dqz_store* S, const dqz_per_draw* d,
+                                  dqz_optimizer* o, int32_t* count, void* stream) {
+  if (int rc = check_step_opt(L, P, o, count)) return rc;
+  if (int rc = per_draw_step(L, P, S, d, o->grad, stream)) return rc;
+  return dqz_optimizer_apply(o, P->online, o->grad, P->mu, P->nu, count, stream);
 }
 
 int dqz_per_add(double* tree, int64_t cap, int32_t remove_index, int32_t add_index, double priority,

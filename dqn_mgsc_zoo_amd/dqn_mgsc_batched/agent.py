@@ -31,6 +31,11 @@ class MGSCDqn(agent_base.DeviceDqnAgent):
                learn_period: int, target_network_update_period: int,
                grad_error_bound: float, rng_key, meta_optimizer=None,
                meta_batch_size: int = 100, device='cuda'):
+    if optimizer is not None and not learner_lib.is_centered_rmsprop(optimizer):
+      raise ValueError(
+          'the MGSC meta-gradient differentiates through the centered-RMSProp '
+          'update of the agent optimizer; pass rmsprop(..., centered=True), '
+          'not Adam, plain RMSProp or a clipped chain')
     super().__init__(preprocessor, sample_network_input, network, optimizer,
                      transition_accumulator, replay, batch_size,
                      exploration_epsilon, min_replay_capacity_fraction,

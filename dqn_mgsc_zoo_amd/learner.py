@@ -3,7 +3,9 @@
 `Learner.step(store, slots)` is the jitted `update` of the reference
 (dqn/agent.py:109-119, double_q/agent.py, prioritized/agent.py:115-127):
 forward of online(s_tm1) and target(s_t) [and online(s_t)], TD loss with
-clip_gradient, backward and centered RMSProp, in place.  Everything runs in
+clip_gradient, backward and the optimizer, in place: centered RMSProp fused
+into the step (the default), or Adam / plain RMSProp, optionally behind
+clip_by_global_norm, applied to the step's finished gradient.  Everything runs in
 libdqz.so on the current HIP stream; there is no host fallback.
 """
 
@@ -21,24 +23,79 @@ ALGOS = {'dqn': _native.ALGO_DQN, 'double': _native.ALGO_DOUBLE,
 
 
 class RMSPropConfig:
-  """optax.rmsprop(learning_rate, decay, eps, centered=True) stand-in."""
+  """optax.rmsprop(learning_rate, decay, eps, centered) stand-in.
+
+  centered=True (dqn/run_atari.py:208-213) is fused into the learner step's
+  kernels; centered=False (scale_by_rms: nu only, eps inside the root) is
+  applied to the finished gradient by dqz_optimizer_apply."""
 
   def __init__(self, learning_rate, decay=0.9, eps=1e-8, centered=False):
-    if not centered:
-      raise NotImplementedError(
-          'only centered RMSProp is on the hot path (dqn/run_atari.py:208-213)')
     self.learning_rate = float(learning_rate)
     self.decay = float(decay)
     self.eps = float(eps)
-    self.centered = True
+    self.centered = bool(centered)
 
 
 def rmsprop(learning_rate, decay=0.9, eps=1e-8, centered=False):
   return RMSPropConfig(learning_rate, decay, eps, centered)
 
 
+class ClipByGlobalNorm:
+  """optax.clip_by_global_norm(max_norm) stand-in: the first stage of a chain."""
+
+  def __init__(self, max_norm):
+    self.max_norm = float(max_norm)
+    if not self.max_norm > 0.0:
+      raise ValueError('max_norm must be positive')
+
+
+def clip_by_global_norm(max_norm):
+  return ClipByGlobalNorm(max_norm)
+
+
+class Chain:
+  """optax.chain(clip_by_global_norm(c), optimizer) stand-in
+  (c51/run_atari.py:210-216): the only chain the device applies."""
+
+  def __init__(self, clip, optimizer):
+    self.clip = clip
+    self.optimizer = optimizer
+    self.learning_rate = optimizer.learning_rate
+
+
+def chain(*transforms):
+  if (len(transforms) != 2 or not isinstance(transforms[0], ClipByGlobalNorm)
+      or not isinstance(transforms[1], (AdamConfig, RMSPropConfig))):
+    raise NotImplementedError(
+        'only chain(clip_by_global_norm(c), adam(...) | rmsprop(...)) is '
+        'supported')
+  if getattr(transforms[1], 'centered', False):
+    raise NotImplementedError(
+        'centered RMSProp is fused into the learner step and cannot follow a '
+        'gradient clip; use adam or rmsprop(centered=False)')
+  return Chain(*transforms)
+
+
+def split_optimizer(optimizer):
+  """(max_norm or None, AdamConfig | RMSPropConfig) of an accepted optimizer."""
+  if isinstance(optimizer, Chain):
+    return optimizer.clip.max_norm, optimizer.optimizer
+  if isinstance(optimizer, (AdamConfig, RMSPropConfig)):
+    return None, optimizer
+  raise NotImplementedError(
+      'optimizer must be rmsprop(...), adam(...) or chain(clip_by_global_norm'
+      '(c), one of them); got %r' % (optimizer,))
+
+
+def is_centered_rmsprop(optimizer):
+  """True for the fused default (what the MGSC meta-gradient differentiates)."""
+  return isinstance(optimizer, RMSPropConfig) and optimizer.centered
+
+
 class Learner:
-  """Online/target params + RMSProp moments in HBM and a libdqz handle."""
+  """Online/target params + optimizer moments in HBM and a libdqz handle."""
+
+  _opt_h = None  # dqz_optimizer handle; None: centered RMSProp, fused into the step
 
   def __init__(self, network: networks_lib.NetworkSpec, batch_size, algo='dqn',
                optimizer=None, grad_error_bound=1.0 / 32, device='cuda'):
@@ -64,14 +121,33 @@ class Learner:
                              dtype=torch.float32, device=self.device)
     self.td = torch.zeros((self.batch_size,), dtype=torch.float32, device=self.device)
     self.loss = torch.zeros((1,), dtype=torch.float32, device=self.device)
+    self.clip_norm, base = split_optimizer(optimizer)
+    self.base_optimizer = base
     cfg = _native.DqzLearnerConfig(
         self.batch_size, network.num_actions, ALGOS[algo],
-        optimizer.learning_rate, optimizer.decay, optimizer.eps,
+        base.learning_rate, getattr(base, 'decay', 0.0), base.eps,
         float(grad_error_bound))
     handle = ctypes.c_void_p()
     _native.check(_native.lib().dqz_learner_create(ctypes.byref(cfg),
                                                    ctypes.byref(handle)))
     self._h = handle
+    # Adam / plain RMSProp / a clipped chain: the step runs in gradient mode
+    # and dqz_optimizer_apply follows it (centered RMSProp stays fused).
+    self._opt_h = None
+    self.count = torch.zeros((1,), dtype=torch.int32, device=self.device)
+    self._gnorm = torch.zeros((1,), dtype=torch.float32, device=self.device)
+    if not is_centered_rmsprop(optimizer):
+      is_adam = isinstance(base, AdamConfig)
+      ocfg = _native.DqzOptimizerConfig(
+          _native.OPT_ADAM if is_adam else _native.OPT_RMSPROP,
+          base.learning_rate, getattr(base, 'b1', 0.0), getattr(base, 'b2', 0.0),
+          getattr(base, 'decay', 0.0), base.eps,
+          self.clip_norm if self.clip_norm is not None else 0.0,
+          network.num_actions, int(bool(network.shared_bias)))
+      oh = ctypes.c_void_p()
+      _native.check(_native.lib().dqz_optimizer_create(ctypes.byref(ocfg),
+                                                       ctypes.byref(oh)))
+      self._opt_h = oh
     self._params_c = _native.DqzParams(
         self.online.data_ptr(), self.target.data_ptr(), self.mu.data_ptr(),
         self.nu.data_ptr())
@@ -81,6 +157,10 @@ class Learner:
     if h is not None and h.value and _native is not None and _native._lib is not None:  # pylint: disable=protected-access
       _native.lib().dqz_learner_destroy(h)
       self._h = None
+      oh = getattr(self, '_opt_h', None)
+      if oh is not None and oh.value:
+        _native.lib().dqz_optimizer_destroy(oh)
+        self._opt_h = None
 
   # -- state -------------------------------------------------------------
 
@@ -95,6 +175,38 @@ class Learner:
   def set_opt_state(self, mu_tree, nu_tree):
     self.mu.copy_(torch.from_numpy(self.network.flatten(mu_tree)))
     self.nu.copy_(torch.from_numpy(self.network.flatten(nu_tree)))
+
+  def opt_state(self):
+    """The optimizer's state in optax's shape (optim_state), host arrays."""
+    base = self.base_optimizer
+    if isinstance(base, AdamConfig):
+      inner = optim_state.adam_state(int(self.count.item()),
+                                     self.params_tree('mu'),
+                                     self.params_tree('nu'))
+    elif base.centered:
+      inner = optim_state.rmsprop_state(self.params_tree('mu'),
+                                        self.params_tree('nu'))
+    else:
+      inner = optim_state.rms_state(self.params_tree('nu'))
+    return inner if self.clip_norm is None else optim_state.chained_state(inner)
+
+  def load_opt_state(self, state):
+    """Restores what opt_state() returned (centered RMSProp also takes the
+    older forms optim_state.rmsprop_moments accepts)."""
+    base = self.base_optimizer
+    if self.clip_norm is not None:
+      state = optim_state.chained_inner(state)
+    if isinstance(base, AdamConfig):
+      count, mu, nu = optim_state.adam_moments(state)
+      self.set_opt_state(mu, nu)
+      self.count.fill_(int(count))
+    elif base.centered:
+      if 'count' in getattr(state[0], '_fields', ()):
+        raise ValueError('an Adam state cannot restore a centered-RMSProp learner')
+      self.set_opt_state(*optim_state.rmsprop_moments(state))
+    else:
+      self.nu.copy_(torch.from_numpy(
+          self.network.flatten(optim_state.rms_moments(state))))
 
   def params_tree(self, which='online'):
     t = {'online': self.online, 'target': self.target, 'mu': self.mu,
@@ -119,6 +231,17 @@ class Learner:
       raise ValueError('slots must be a device int32 tensor of batch size')
     if self.algo == 'per' and weights is None:
       raise ValueError('PER step needs importance weights')
+    if self._opt_h is not None:
+      _native.check(_native.lib().dqz_learner_step_opt(
+          self._h, ctypes.byref(self._params_c), store.c_ref(),
+          _native.ptr(slots), _native.ptr(weights), self._opt_h,
+          _native.ptr(self.count), _native.stream_handle(stream)))
+      if write_back is not None:  # its own launch: it reads the step's td
+        tree, cap, indices, alpha, max_seen = write_back
+        _native.check(_native.lib().dqz_per_write_back(
+            self._h, _native.ptr(tree), int(cap), _native.ptr(indices),
+            float(alpha), _native.ptr(max_seen), _native.stream_handle(stream)))
+      return
     if write_back is not None:
       tree, cap, indices, alpha, max_seen = write_back
       _native.check(_native.lib().dqz_learner_step_per(
@@ -140,6 +263,13 @@ class Learner:
     """
     if slots_out.dtype != torch.int32 or slots_out.numel() != self.batch_size:
       raise ValueError('slots_out must be a device int32 tensor of batch size')
+    if self._opt_h is not None:
+      _native.check(_native.lib().dqz_learner_step_opt_uniform(
+          self._h, ctypes.byref(self._params_c), store.c_ref(), int(base),
+          int(size), int(capacity), int(seed) & (2**64 - 1),
+          _native.ptr(counter), _native.ptr(slots_out), self._opt_h,
+          _native.ptr(self.count), _native.stream_handle(stream)))
+      return
     _native.check(_native.lib().dqz_learner_step_uniform(
         self._h, ctypes.byref(self._params_c), store.c_ref(), int(base),
         int(size), int(capacity), int(seed) & (2**64 - 1), _native.ptr(counter),
@@ -161,6 +291,7 @@ class Learner:
       raise ValueError('slots_out must be a device int32 tensor of batch size')
     if (counter is None) == (uniforms is None):
       raise ValueError('pass exactly one of counter (Philox) and uniforms')
+    self._need_fused_rmsprop('step_logits')
     lib = _native.lib()
     fn = lib.dqz_learner_step_logits_exact if exact else lib.dqz_learner_step_logits
     _native.check(fn(
@@ -177,6 +308,12 @@ class Learner:
     replay.PrioritizedTransitionReplay.per_draw)."""
     if self.algo != 'per':
       raise ValueError('step_per_draw needs a PER learner')
+    if self._opt_h is not None:
+      _native.check(_native.lib().dqz_learner_step_opt_per_draw(
+          self._h, ctypes.byref(self._params_c), store.c_ref(),
+          ctypes.byref(draw), self._opt_h, _native.ptr(self.count),
+          _native.stream_handle(stream)))
+      return
     _native.check(_native.lib().dqz_learner_step_per_draw(
         self._h, ctypes.byref(self._params_c), store.c_ref(), ctypes.byref(draw),
         _native.stream_handle(stream)))
@@ -194,6 +331,7 @@ class Learner:
 
   def profile(self, store, slots, weights=None, iters=20, stream=None):
     """Average ms per phase (HIP events on the launch stream), dict."""
+    self._need_fused_rmsprop('profile')
     out = (ctypes.c_float * _native.NUM_PHASES)()
     _native.check(_native.lib().dqz_learner_profile(
         self._h, ctypes.byref(self._params_c), store.c_ref(),
@@ -203,6 +341,25 @@ class Learner:
     names = list(_native.PHASE_NAMES)
     # phases merged into another launch report 0 and are left out
     return {n: t for n, t in zip(names, ms) if t > 0.0}
+
+  def _need_fused_rmsprop(self, what):
+    if self._opt_h is not None:
+      raise NotImplementedError(
+          '%s runs the fused centered-RMSProp step only; this learner applies '
+          '%s after the step (dqz_learner_step_opt*)' % (
+              what, type(self.base_optimizer).__name__))
+
+  def grad_norm(self, stream=None):
+    """Global norm of the last step's gradient, before clipping: a device
+    f32 [1] tensor (dqz_optimizer_outputs).  Adam / plain RMSProp / clipped
+    chains only; the fused centered-RMSProp step keeps no gradient."""
+    if self._opt_h is None:
+      raise NotImplementedError(
+          'the fused centered-RMSProp step does not keep its gradient; use '
+          'Learner.grad()')
+    _native.check(_native.lib().dqz_optimizer_outputs(
+        self._opt_h, _native.ptr(self._gnorm), _native.stream_handle(stream)))
+    return self._gnorm
 
   def fetch_outputs(self, stream=None):
     """Copies (q_tm1, td, loss) of the last step into self tensors."""
@@ -367,6 +524,11 @@ class MetaLearner:
     from dqn_mgsc_zoo_amd import store as store_lib  # pylint: disable=g-import-not-at-top
     if learner.algo != 'dqn':
       raise ValueError('the MGSC agents use q_learning on dqn_atari_network')
+    if not is_centered_rmsprop(learner.optimizer):
+      raise ValueError(
+          'the MGSC meta-gradient differentiates through the centered-RMSProp '
+          'update of the learner (theta\' = theta + u(G; mu, nu)); the agent '
+          'optimizer must be rmsprop(..., centered=True)')
     meta_optimizer = meta_optimizer or adam(2.5e-4)
     self.learner = learner
     self.meta_batch_size = int(meta_batch_size)

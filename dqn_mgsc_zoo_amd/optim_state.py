@@ -10,6 +10,12 @@ dqn_mgsc_batched/agent.py:381-400), so its values are optax 0.1.2 states
 * `optax.adam` (dqn_mgsc_batched/run_atari.py:241-243) is
   chain(scale_by_adam, scale(-lr)): `(ScaleByAdamState(count, mu, nu),
   EmptyState())`, over the [meta_batch] logit vector;
+* `optax.rmsprop(centered=False)` is chain(scale_by_rms, scale(-lr)):
+  `(ScaleByRmsState(nu), EmptyState())`;
+* `optax.chain(optax.clip_by_global_norm(c), optimizer)`
+  (c51/run_atari.py:210-216) nests the optimizer's own chain state behind the
+  clip's empty one: `(EmptyState(), (ScaleByAdamState(count, mu, nu),
+  EmptyState()))`, mu / nu Haiku trees;
 * the key is an array of uint32.  Here the acting stream is Philox-4x32, so
   the key is uint32[4] = (seed lo, seed hi, counter lo, counter hi): the
   64-bit key and the 64-bit draw counter, JAX's uint32[2] threefry key
@@ -43,8 +49,13 @@ class ScaleByAdamState(NamedTuple):
   nu: Any
 
 
+class ScaleByRmsState(NamedTuple):
+  """optax.ScaleByRmsState (plain RMSProp's second moment)."""
+  nu: Any
+
+
 class EmptyState(NamedTuple):
-  """optax.EmptyState (the scale(-lr) stage)."""
+  """optax.EmptyState (the scale(-lr) stage; clip_by_global_norm's state)."""
 
 
 _M32 = 0xFFFFFFFF
@@ -98,3 +109,29 @@ def adam_moments(opt_state):
     return int(opt_state['count']), opt_state['mu'], opt_state['nu']
   first = opt_state[0]
   return int(first.count), first.mu, first.nu
+
+
+def rms_state(nu):
+  return (ScaleByRmsState(nu=nu), EmptyState())
+
+
+def rms_moments(opt_state):
+  """nu from a plain-rmsprop state tuple."""
+  first = opt_state[0]
+  if not hasattr(first, 'nu') or hasattr(first, 'mu'):
+    raise ValueError('expected (ScaleByRmsState(nu), EmptyState())')
+  return first.nu
+
+
+def chained_state(inner):
+  """State of chain(clip_by_global_norm(c), optimizer): inner = the
+  optimizer's own state tuple."""
+  return (EmptyState(), inner)
+
+
+def chained_inner(opt_state):
+  """The optimizer's own state from a chained_state."""
+  if (len(opt_state) != 2 or len(opt_state[0]) != 0
+      or isinstance(opt_state[0], dict)):
+    raise ValueError('expected (EmptyState(), optimizer state)')
+  return opt_state[1]

@@ -564,6 +564,80 @@ typedef struct dqz_per_draw {
 int dqz_learner_step_per_draw(dqz_learner* learner, const dqz_params* params, const dqz_store* store,
                               const dqz_per_draw* draw, void* stream);
 
+/* ---- optimizers on a finished gradient -----------------------------------
+ * optax.adam, plain optax.rmsprop(centered=False) and
+ * optax.clip_by_global_norm in front of either (optax 0.1.2; the chain of
+ * c51/run_atari.py:210-216, qrdqn, iqn and rainbow).  Centered RMSProp is not
+ * here: it is fused into dqz_learner_step's own kernels.
+ *   clip_by_global_norm(c): g <- g if |g| < c else (g / |g|) c, |g| the
+ *     global norm over the ten leaves (padding excluded), summed in float64 in
+ *     a fixed order (equal gradients give equal bits);
+ *   DQZ_OPT_ADAM (scale_by_adam, eps_root = 0; scale(-lr)):
+ *     m <- b1 m + (1 - b1) g;  v <- b2 v + (1 - b2) g^2;  count <- count + 1;
+ *     theta <- theta - lr (m / (1 - b1^count)) / (sqrt(v / (1 - b2^count)) + eps)
+ *   DQZ_OPT_RMSPROP (scale_by_rms; scale(-lr)):
+ *     nu <- decay nu + (1 - decay) g^2;  theta <- theta - lr g / sqrt(nu + eps)
+ * The arithmetic is float64 inside with IEEE division and square root; theta
+ * and the moments are float32, rounded once per step.  Padding of every leaf
+ * is never written. */
+#define DQZ_OPT_ADAM 0
+#define DQZ_OPT_RMSPROP 1
+
+typedef struct dqz_optimizer_config {
+  int kind;             /* DQZ_OPT_* */
+  float learning_rate;
+  float b1, b2;         /* Adam (0.9, 0.999) */
+  float decay;          /* RMSProp (0.9) */
+  float eps;
+  float max_global_grad_norm; /* <= 0: no clipping */
+  int num_actions;      /* the parameter layout, as dqz_param_layout */
+  int shared_bias;
+} dqz_optimizer_config;
+
+typedef struct dqz_optimizer dqz_optimizer;
+
+/* The handle owns a gradient scratch [total] (zeroed once: the learner's
+ * gradient mode leaves padding untouched) and the norm's float64 partials.
+ * Calls on one handle must be ordered on one stream. */
+int dqz_optimizer_create(const dqz_optimizer_config* cfg, dqz_optimizer** out);
+int dqz_optimizer_destroy(dqz_optimizer* opt);
+
+/* The optimizer on a caller-supplied gradient (device f32 [total], dqz
+ * parameter layout; its padding is ignored): the norm launch when clipping,
+ * then one apply launch, in place on params_online and the moments.
+ *   Adam: mu = m, nu = v (device f32 [total]); count: device int32 [1]
+ *     (ScaleByAdamState.count), advanced on the device exactly once, by a
+ *     one-thread launch behind the apply whose workgroups read it.
+ *   RMSProp: nu (ScaleByRmsState.nu); mu and count are ignored (may be NULL).
+ * No host synchronisation, no allocation, capturable in a graph. */
+int dqz_optimizer_apply(dqz_optimizer* opt, float* params_online, const float* grad, float* mu, float* nu,
+                        int32_t* count, void* stream);
+
+/* *gnorm (device f32 [1]) = the global norm, before clipping, of the gradient
+ * of the handle's most recent step or apply.  With clipping it is a copy of
+ * the value that step used; without, it is computed now from that gradient
+ * (the handle's scratch after a step; after a stand-alone apply the caller's
+ * buffer, which must still hold the gradient). */
+int dqz_optimizer_outputs(dqz_optimizer* opt, float* gnorm, void* stream);
+
+/* dqz_learner_step, dqz_learner_step_uniform and dqz_learner_step_per_draw
+ * with one of the optimizers above in place of centered RMSProp: the same
+ * step in gradient mode into the handle's scratch (forward, TD loss, health
+ * word, the fused draw, the PER weights and write-back as in the plain call;
+ * the learner config's learning_rate / decay / eps are unused), then
+ * dqz_optimizer_apply on params->online / mu / nu and `count`.  The optimizer
+ * must have the learner's num_actions and bias shape.  Same stream, no
+ * allocation, capturable in a graph. */
+int dqz_learner_step_opt(dqz_learner* learner, const dqz_params* params, const dqz_store* store,
+                         const int32_t* slots, const float* is_weights, dqz_optimizer* opt, int32_t* count,
+                         void* stream);
+int dqz_learner_step_opt_uniform(dqz_learner* learner, const dqz_params* params, const dqz_store* store,
+                                 int64_t base, int64_t size, int64_t capacity, uint64_t seed,
+                                 uint64_t* counter_dev, int32_t* slots_out, dqz_optimizer* opt, int32_t* count,
+                                 void* stream);
+int dqz_learner_step_opt_per_draw(dqz_learner* learner, const dqz_params* params, const dqz_store* store,
+                                  const dqz_per_draw* draw, dqz_optimizer* opt, int32_t* count, void* stream);
+
 /* PrioritizedTransitionReplay.add on device (replay.py:1068-1096 ->
  * PrioritizedDistribution.remove_priorities / add_priorities, :642-678): the
  * evicted tree index remove_index (-1: none) is set to 0, add_index to

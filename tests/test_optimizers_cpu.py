@@ -1,0 +1,216 @@
+"""CPU: the float64 restatement of the new optimizers (tests/optim_ref.py),
+the optimizer configs learner.py accepts and rejects, and the optax-shaped
+states of optim_state.py (Adam / plain RMSProp / a clipped chain)."""
+
+import pickle
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from dqn_mgsc_zoo_amd import learner as learner_lib
+from dqn_mgsc_zoo_amd import optim_state as os_
+from oracle import learner_ref
+from tests import optim_ref
+
+
+def _tree(rng, scale=1.0):
+  return {'conv': {'w': scale * rng.standard_normal((3, 4)), 'b': scale * rng.standard_normal(4)},
+          'linear': {'w': scale * rng.standard_normal((4, 2)), 'b': scale * rng.standard_normal(1)}}
+
+
+@pytest.mark.parametrize('eps', [1e-8, 0.01 / 32])
+def test_adam_ref_equals_torch_adam_in_float64(eps):
+  rng = np.random.default_rng(0)
+  lr, b1, b2 = 2.5e-4, 0.9, 0.999
+  theta = rng.standard_normal(257)
+  p = torch.tensor(theta, dtype=torch.float64, requires_grad=True)
+  opt = torch.optim.Adam([p], lr=lr, betas=(b1, b2), eps=eps)
+  m, v, count = np.zeros_like(theta), np.zeros_like(theta), 0
+  for _ in range(5):
+    g = rng.standard_normal(257) * 10.0 ** rng.integers(-6, 3, 257)
+    p.grad = torch.tensor(g, dtype=torch.float64)
+    opt.step()
+    theta, m, v, count = optim_ref.adam(theta, g, m, v, count, lr, b1, b2, eps)
+    np.testing.assert_allclose(theta, p.detach().numpy(), rtol=1e-12, atol=0)
+  assert count == 5
+  # the oracle's own flat adam says the same
+  t2, m2, v2, c2 = learner_ref.adam(theta, g, m, v, count, lr, b1, b2, eps)
+  t1, m1, v1, c1 = optim_ref.adam(theta, g, m, v, count, lr, b1, b2, eps)
+  np.testing.assert_allclose(t1, t2, rtol=1e-14)
+  np.testing.assert_allclose(v1, v2, rtol=1e-15)
+  assert c1 == c2 == 6
+
+
+def test_adam_ref_on_trees_matches_its_leaves():
+  rng = np.random.default_rng(1)
+  th, g, m = _tree(rng), _tree(rng), _tree(rng, 1e-2)
+  v = {k: {n: x * x + 1e-4 for n, x in d.items()} for k, d in m.items()}
+  t1, m1, v1, c = optim_ref.adam(th, g, m, v, 7, 1e-3)
+  assert c == 8
+  for k in th:
+    for n in th[k]:
+      a, b_, c_, _ = optim_ref.adam(th[k][n], g[k][n], m[k][n], v[k][n], 7, 1e-3)
+      np.testing.assert_array_equal(t1[k][n], a)
+      np.testing.assert_array_equal(m1[k][n], b_)
+      np.testing.assert_array_equal(v1[k][n], c_)
+  u = optim_ref.adam_update(g, m, v, 7, 1e-3)
+  np.testing.assert_allclose(th['conv']['w'] - u['conv']['w'], t1['conv']['w'], rtol=1e-15)
+
+
+def test_rmsprop_ref_known_answer():
+  # nu = 0.9 * 4 + 0.1 * 9 = 4.5; step = 0.5 * 3 / sqrt(4.5 + 0.5)
+  th, nu = optim_ref.rmsprop(np.array([1.0]), np.array([3.0]), np.array([4.0]), 0.5, 0.9, 0.5)
+  np.testing.assert_allclose(nu, [4.5], rtol=1e-15)
+  np.testing.assert_allclose(th, [1.0 - 1.5 / np.sqrt(5.0)], rtol=1e-15)
+  # eps is inside the root: a zero gradient on zero state does not move
+  th, nu = optim_ref.rmsprop(np.array([1.0]), np.array([0.0]), np.array([0.0]), 0.5, 0.9, 1e-8)
+  assert th[0] == 1.0 and nu[0] == 0.0
+
+
+def test_clip_by_global_norm_known_answers():
+  g = {'a': {'w': np.array([3.0, 0.0])}, 'b': {'w': np.array([[0.0], [4.0]])}}
+  assert optim_ref.global_norm(g) == 5.0
+  # below the threshold: untouched
+  c, n = optim_ref.clip_by_global_norm(g, 10.0)
+  assert n == 5.0
+  np.testing.assert_array_equal(c['a']['w'], [3.0, 0.0])
+  np.testing.assert_array_equal(c['b']['w'], [[0.0], [4.0]])
+  # above: scaled to norm max_norm
+  c, n = optim_ref.clip_by_global_norm(g, 2.5)
+  assert n == 5.0
+  np.testing.assert_allclose(c['a']['w'], [1.5, 0.0], rtol=1e-15)
+  np.testing.assert_allclose(c['b']['w'], [[0.0], [2.0]], rtol=1e-15)
+  np.testing.assert_allclose(optim_ref.global_norm(c), 2.5, rtol=1e-15)
+  # at the threshold the trigger |g| < c is false: (g / |g|) * c
+  c, _ = optim_ref.clip_by_global_norm(g, 5.0)
+  np.testing.assert_allclose(c['b']['w'], [[0.0], [4.0]], rtol=1e-15)
+  # a zero gradient is below any positive threshold
+  z, n = optim_ref.clip_by_global_norm(np.zeros(3), 1.0)
+  assert n == 0.0 and not z.any()
+
+
+def test_state_shapes_round_trip():
+  rng = np.random.default_rng(2)
+  mu, nu = _tree(rng), _tree(rng)
+  # plain RMSProp
+  st = os_.rms_state(nu)
+  assert type(st[0]).__name__ == 'ScaleByRmsState' and st[0]._fields == ('nu',)
+  assert st[1] == os_.EmptyState()
+  back = pickle.loads(pickle.dumps(st))
+  np.testing.assert_array_equal(os_.rms_moments(back)['conv']['w'], nu['conv']['w'])
+  # Adam over Haiku trees
+  st = os_.adam_state(3, mu, nu)
+  count, m2, n2 = os_.adam_moments(pickle.loads(pickle.dumps(st)))
+  assert count == 3
+  np.testing.assert_array_equal(m2['linear']['b'], mu['linear']['b'])
+  np.testing.assert_array_equal(n2['linear']['w'], nu['linear']['w'])
+  # chain(clip_by_global_norm, adam)
+  ch = os_.chained_state(st)
+  assert ch[0] == os_.EmptyState() and len(ch) == 2
+  assert type(ch[1][0]).__name__ == 'ScaleByAdamState' and ch[1][1] == os_.EmptyState()
+  inner = os_.chained_inner(pickle.loads(pickle.dumps(ch)))
+  assert os_.adam_moments(inner)[0] == 3
+  # chain(clip_by_global_norm, rmsprop)
+  assert os_.rms_moments(os_.chained_inner(os_.chained_state(os_.rms_state(nu)))) is nu
+  # an unchained state is not mistaken for a chained one, nor a centered for a plain one
+  with pytest.raises(ValueError):
+    os_.chained_inner(st)
+  with pytest.raises(ValueError):
+    os_.rms_moments(os_.rmsprop_state(mu, nu))
+
+
+def test_accepted_and_rejected_optimizers():
+  adam, clip = learner_lib.adam(2.5e-4, eps=0.01 / 32), learner_lib.clip_by_global_norm(10.0)
+  plain = learner_lib.rmsprop(1e-3)  # centered=False no longer raises
+  centered = learner_lib.rmsprop(2.5e-4, 0.95, 1e-5, centered=True)
+  assert not plain.centered and centered.centered
+  assert learner_lib.split_optimizer(adam) == (None, adam)
+  assert learner_lib.split_optimizer(plain) == (None, plain)
+  assert learner_lib.split_optimizer(centered) == (None, centered)
+  ch = learner_lib.chain(clip, adam)
+  assert learner_lib.split_optimizer(ch) == (10.0, adam)
+  assert ch.learning_rate == adam.learning_rate
+  assert learner_lib.split_optimizer(learner_lib.chain(clip, plain)) == (10.0, plain)
+  assert learner_lib.is_centered_rmsprop(centered)
+  for opt in (adam, plain, ch):
+    assert not learner_lib.is_centered_rmsprop(opt)
+  for bad in ((adam, clip), (clip,), (clip, adam, adam), (clip, clip), (adam, adam), (clip, centered), ()):
+    with pytest.raises(NotImplementedError):
+      learner_lib.chain(*bad)
+  with pytest.raises(NotImplementedError):
+    learner_lib.split_optimizer(clip)  # a clip alone optimizes nothing
+  with pytest.raises(NotImplementedError):
+    learner_lib.split_optimizer(object())
+  with pytest.raises(ValueError):
+    learner_lib.clip_by_global_norm(0.0)
+  with pytest.raises(NotImplementedError):
+    learner_lib.adam(1e-3, eps_root=1e-8)
+
+
+class _FakeLearner:
+  """Learner.opt_state / load_opt_state without a device: trees in, trees out."""
+
+  opt_state = learner_lib.Learner.opt_state
+  load_opt_state = learner_lib.Learner.load_opt_state
+
+  def __init__(self, optimizer):
+    self.clip_norm, self.base_optimizer = learner_lib.split_optimizer(optimizer)
+    self.trees = {}
+    self.count = types.SimpleNamespace(v=0)
+    self.count.item = lambda: self.count.v
+    self.count.fill_ = lambda x: setattr(self.count, 'v', int(x))
+    self.network = types.SimpleNamespace(flatten=lambda tree: np.zeros(1, np.float32))
+    self.nu = types.SimpleNamespace(copy_=lambda t: None)
+
+  def params_tree(self, which):
+    return self.trees[which]
+
+  def set_opt_state(self, mu, nu):
+    self.trees['mu'], self.trees['nu'] = mu, nu
+
+
+def test_old_rmsprop_checkpoint_still_loads():
+  rng = np.random.default_rng(3)
+  mu, nu = _tree(rng), _tree(rng)
+  lrn = _FakeLearner(learner_lib.rmsprop(2.5e-4, 0.95, 1e-5, centered=True))
+  for old in (os_.rmsprop_state(mu, nu), (mu, nu),
+              pickle.loads(pickle.dumps(os_.rmsprop_state(mu, nu)))):
+    lrn.trees = {}
+    lrn.load_opt_state(old)
+    np.testing.assert_array_equal(lrn.trees['mu']['conv']['w'], mu['conv']['w'])
+    np.testing.assert_array_equal(lrn.trees['nu']['linear']['b'], nu['linear']['b'])
+  # and what the centered learner emits is the shape it always emitted
+  st = lrn.opt_state()
+  assert type(st[0]).__name__ == 'ScaleByRStdDevState' and st[1] == os_.EmptyState()
+
+
+def test_learner_state_shape_follows_its_optimizer():
+  rng = np.random.default_rng(4)
+  mu, nu = _tree(rng), _tree(rng)
+  clip = learner_lib.clip_by_global_norm(10.0)
+  a = _FakeLearner(learner_lib.chain(clip, learner_lib.adam(1e-3)))
+  a.trees = {'mu': mu, 'nu': nu}
+  a.count.v = 9
+  st = a.opt_state()
+  assert st[0] == os_.EmptyState() and st[1][0].count == 9 and st[1][0].count.dtype == np.int32
+  b = _FakeLearner(learner_lib.chain(clip, learner_lib.adam(1e-3)))
+  b.load_opt_state(pickle.loads(pickle.dumps(st)))
+  assert b.count.v == 9
+  np.testing.assert_array_equal(b.trees['mu']['conv']['b'], mu['conv']['b'])
+  # an unclipped Adam learner emits and takes the unchained state
+  c = _FakeLearner(learner_lib.adam(1e-3))
+  c.trees = {'mu': mu, 'nu': nu}
+  assert type(c.opt_state()[0]).__name__ == 'ScaleByAdamState'
+  with pytest.raises(ValueError):
+    b.load_opt_state(c.opt_state())
+  # nor does an Adam state pass for centered RMSProp's (both carry mu and nu)
+  fused = _FakeLearner(learner_lib.rmsprop(2.5e-4, 0.95, 1e-5, centered=True))
+  with pytest.raises(ValueError):
+    fused.load_opt_state(c.opt_state())
+  r = _FakeLearner(learner_lib.rmsprop(1e-3))
+  r.trees = {'nu': nu}
+  st = r.opt_state()
+  assert type(st[0]).__name__ == 'ScaleByRmsState' and st[0].nu is nu
+  r.load_opt_state(st)
