@@ -520,7 +520,7 @@ int dqz_learner_step_logits(dqz_learner* L, const dqz_params* P, const dqz_store
   if (int rc = ensure_run(buf, logits, st)) return rc;
   SoftmaxDraw sm{logits, buf->capacity, buf->run, buf->csum, buf->nblocks,
                  seed,   uniforms ? nullptr : counter_dev,    uniforms,  slots_out};
-  return step_impl(L, P, S, slots_out, nullptr, stream, kNoProfile, nullptr, nullptr, nullptr, 0, 0, nullptr, &sm);
+  return step_impl(L, P, S, {.sm = &sm}, stream);
 }
 
 int dqz_learner_step_logits_exact(dqz_learner* L, const dqz_params* P, const dqz_store* S, dqz_logit_buffer* buf,
@@ -530,16 +530,13 @@ int dqz_learner_step_logits_exact(dqz_learner* L, const dqz_params* P, const dqz
   if (!counter_dev == !uniforms) return fail(DQZ_ERR_INVALID, "give exactly one of counter_dev and uniforms");
   if (L->cfg.algo == DQZ_ALGO_PER) return fail(DQZ_ERR_INVALID, "PER samples by priority, not by learned logits");
   if (buf->capacity > INT32_MAX) return fail(DQZ_ERR_INVALID, "int32 slots need capacity < 2^31");
-  // the step's own checks first: nothing is enqueued for a call that fails
-  if (!P || !P->online || !P->target) return fail(DQZ_ERR_INVALID, "null argument");
-  if (!P->mu || !P->nu) return fail(DQZ_ERR_INVALID, "null optimizer state");
-  if (int rc = check_store(S)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = npx_prepare(buf, logits, nullptr, st)) return rc;
   SoftmaxDrawExact smx{logits, buf->capacity, buf->scal_x, buf->csum_x, buf->nblocks,
                        seed,   counter_dev,   uniforms,    slots_out};
-  return step_impl(L, P, S, slots_out, nullptr, stream, kNoProfile, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr,
-                   nullptr, nullptr, nullptr, nullptr, &smx);
+  const StepRequest r{.smx = &smx};
+  // the step's own checks first: nothing is enqueued for a call that fails
+  if (int rc = check_step(L, P, S, r)) return rc;
+  if (int rc = npx_prepare(buf, logits, nullptr, (hipStream_t)stream)) return rc;
+  return step_enqueue(L, P, S, r, stream);
 }
 
 int dqz_uniform_philox(uint64_t seed, uint64_t* counter_dev, int n, double* out, void* stream) {
@@ -547,12 +544,6 @@ int dqz_uniform_philox(uint64_t seed, uint64_t* counter_dev, int n, double* out,
   hipLaunchKernelGGL(philox_uniform_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, seed, counter_dev, n, out);
   DQZ_HIP(hipGetLastError());
   return DQZ_OK;
-}
-
-static int tree_levels(int64_t cap) {
-  int l = 0;
-  while ((int64_t(1) << l) < cap) ++l;
-  return l;
 }
 
 int dqz_sumtree_set(double* tree, int64_t cap, const int64_t* idx, const double* values, int n, void* stream) {
@@ -595,39 +586,32 @@ int dqz_sumtree_query(const double* tree, int64_t cap, const double* targets, in
   return DQZ_OK;
 }
 
+// The prioritized draw's checks on its filled kernel argument, whose tree levels this sets.  (The learner
+// step's fused draw has n = its batch <= MAXB, so the n check only ever refuses a dqz_per_sample call.)
+static int per_draw_args(PerSampleArgs* a) {
+  if (!a->inj_u && !a->counter) return fail(DQZ_ERR_INVALID, "Philox draws need counter_dev");
+  if ((a->inj_u == nullptr) != (a->inj_uniform == nullptr))
+    return fail(DQZ_ERR_INVALID, "injected_uniform and injected_u go together");
+  if (a->cap < a->capacity || (a->cap & (a->cap - 1))) return fail(DQZ_ERR_INVALID, "cap must be a power of two >= capacity");
+  if (a->size < 1) return fail(DQZ_ERR_INVALID, "No IDs to sample.");
+  if (a->n < 1 || a->n > 1024) return fail(DQZ_ERR_INVALID, "n must be in [1, 1024]");
+  if (!(a->beta >= 0.0 && a->beta <= 1.0)) return fail(DQZ_ERR_INVALID, "Require 0 <= exponent <= 1.");
+  if (!(a->usp >= 0.0 && a->usp <= 1.0)) return fail(DQZ_ERR_INVALID, "Require 0 <= uniform_sample_probability <= 1.");
+  a->levels = tree_levels(a->cap);
+  return DQZ_OK;
+}
+
 int dqz_per_sample(const double* tree, int64_t cap, int64_t live_base, int64_t size, int64_t capacity, int n,
                    double usp, double beta, int normalize, uint64_t seed, uint64_t* counter_dev,
                    const int32_t* injected_uniform, const double* injected_u, const int32_t* index_to_slot,
                    int32_t* out_indices, int32_t* out_slots, float* out_weights, double* out_probs, void* stream) {
   if (!tree || !out_slots || !out_weights) return fail(DQZ_ERR_INVALID, "null argument");
-  if (!injected_u && !counter_dev) return fail(DQZ_ERR_INVALID, "Philox draws need counter_dev");
-  if ((injected_u == nullptr) != (injected_uniform == nullptr))
-    return fail(DQZ_ERR_INVALID, "injected_uniform and injected_u go together");
-  if (cap < capacity || (cap & (cap - 1))) return fail(DQZ_ERR_INVALID, "cap must be a power of two >= capacity");
-  if (size < 1) return fail(DQZ_ERR_INVALID, "No IDs to sample.");
-  if (n < 1 || n > 1024) return fail(DQZ_ERR_INVALID, "n must be in [1, 1024]");
-  if (!(beta >= 0.0 && beta <= 1.0)) return fail(DQZ_ERR_INVALID, "Require 0 <= exponent <= 1.");
-  if (!(usp >= 0.0 && usp <= 1.0)) return fail(DQZ_ERR_INVALID, "Require 0 <= uniform_sample_probability <= 1.");
-  PerSampleArgs a{};
-  a.tree = tree;
-  a.cap = cap;
-  a.levels = tree_levels(cap);
-  a.live_base = live_base;
-  a.size = size;
-  a.capacity = capacity;
-  a.n = n;
-  a.usp = usp;
-  a.beta = beta;
-  a.normalize = normalize;
-  a.seed = seed;
-  a.counter = counter_dev;
-  a.inj_uniform = injected_uniform;
-  a.inj_u = injected_u;
-  a.index_to_slot = index_to_slot;
-  a.out_indices = out_indices;
-  a.out_slots = out_slots;
-  a.out_weights = out_weights;
-  a.out_probs = out_probs;
+  PerSampleArgs a{.tree = tree, .cap = cap, .live_base = live_base, .size = size, .capacity = capacity, .n = n,
+                  .usp = usp, .beta = beta, .normalize = normalize, .seed = seed, .counter = counter_dev,
+                  .inj_uniform = injected_uniform, .inj_u = injected_u, .index_to_slot = index_to_slot,
+                  .out_indices = out_indices, .out_slots = out_slots, .out_weights = out_weights,
+                  .out_probs = out_probs};
+  if (int rc = per_draw_args(&a)) return rc;
   hipLaunchKernelGGL(per_sample_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
   DQZ_HIP(hipGetLastError());
   return DQZ_OK;
@@ -640,40 +624,17 @@ static int per_draw_step(dqz_learner* L, const dqz_params* P, const dqz_store* S
   if (!L || !d || !d->tree || !d->out_indices || !d->out_slots || !d->out_probs || !d->max_seen_dev)
     return fail(DQZ_ERR_INVALID, "null argument");
   if (L->cfg.algo != DQZ_ALGO_PER) return fail(DQZ_ERR_INVALID, "the learner is not a PER learner");
-  if (!d->injected_u && !d->counter_dev) return fail(DQZ_ERR_INVALID, "Philox draws need counter_dev");
-  if ((d->injected_u == nullptr) != (d->injected_uniform == nullptr))
-    return fail(DQZ_ERR_INVALID, "injected_uniform and injected_u go together");
-  if (d->cap < d->capacity || (d->cap & (d->cap - 1))) return fail(DQZ_ERR_INVALID, "cap must be a power of two >= capacity");
-  if (d->size < 1) return fail(DQZ_ERR_INVALID, "No IDs to sample.");
-  const double beta = d->importance_sampling_exponent, usp = d->uniform_sample_probability;
-  if (!(beta >= 0.0 && beta <= 1.0)) return fail(DQZ_ERR_INVALID, "Require 0 <= exponent <= 1.");
-  if (!(usp >= 0.0 && usp <= 1.0)) return fail(DQZ_ERR_INVALID, "Require 0 <= uniform_sample_probability <= 1.");
-  const int levels = tree_levels(d->cap);
-  if (L->cfg.batch > 64 || levels > PWB_LEVELS)
+  PerSampleArgs a{.tree = d->tree, .cap = d->cap, .live_base = d->live_base, .size = d->size,
+                  .capacity = d->capacity, .n = L->cfg.batch, .usp = d->uniform_sample_probability,
+                  .beta = d->importance_sampling_exponent, .normalize = d->normalize_weights, .seed = d->seed,
+                  .counter = d->counter_dev, .inj_uniform = d->injected_uniform, .inj_u = d->injected_u,
+                  .index_to_slot = d->index_to_slot, .out_indices = d->out_indices, .out_slots = d->out_slots,
+                  .out_weights = d->out_weights, .out_probs = d->out_probs};
+  if (int rc = per_draw_args(&a)) return rc;
+  PerWbArgs wb;
+  if (!per_wb_args(L, d->tree, d->cap, d->out_indices, d->alpha, d->max_seen_dev, &wb))
     return fail(DQZ_ERR_INVALID, "the fused PER step takes batch <= 64 and cap <= 2^%d", PWB_LEVELS);
-  PerSampleArgs a{};
-  a.tree = d->tree;
-  a.cap = d->cap;
-  a.levels = levels;
-  a.live_base = d->live_base;
-  a.size = d->size;
-  a.capacity = d->capacity;
-  a.n = L->cfg.batch;
-  a.usp = usp;
-  a.beta = beta;
-  a.normalize = d->normalize_weights;
-  a.seed = d->seed;
-  a.counter = d->counter_dev;
-  a.inj_uniform = d->injected_uniform;
-  a.inj_u = d->injected_u;
-  a.index_to_slot = d->index_to_slot;
-  a.out_indices = d->out_indices;
-  a.out_slots = d->out_slots;
-  a.out_weights = d->out_weights;
-  a.out_probs = d->out_probs;
-  PerWbArgs wb{d->tree, d->cap, levels, d->out_indices, nullptr, d->alpha, 0, d->max_seen_dev};
-  return step_impl(L, P, S, d->out_slots, nullptr, stream, kNoProfile, gout, nullptr, nullptr, 0, 0, &wb, nullptr,
-                   &a);
+  return step_impl(L, P, S, {.pd = &a, .gout = gout, .wb = &wb}, stream);
 }
 
 int dqz_learner_step_per_draw(dqz_learner* L, const dqz_params* P, const dqz_store* S, const dqz_per_draw* d,
@@ -812,7 +773,7 @@ static int check_step_opt(const dqz_learner* L, const dqz_params* P, const dqz_o
 int dqz_learner_step_opt(dqz_learner* L, const dqz_params* P, const dqz_store* S, const int32_t* slots,
                          const float* is_weights, dqz_optimizer* o, int32_t* count, void* stream) {
   if (int rc = check_step_opt(L, P, o, count)) return rc;
-  if (int rc = step_impl(L, P, S, slots, is_weights, stream, kNoProfile, o->grad)) return rc;
+  if (int rc = step_impl(L, P, S, {.slots = slots, .is_weights = is_weights, .gout = o->grad}, stream)) return rc;
   return dqz_optimizer_apply(o, P->online, o->grad, P->mu, P->nu, count, stream);
 }
 
@@ -820,12 +781,9 @@ int dqz_learner_step_opt_uniform(dqz_learner* L, const dqz_params* P, const dqz_
                                  int64_t capacity, uint64_t seed, uint64_t* counter_dev, int32_t* slots_out,
                                  dqz_optimizer* o, int32_t* count, void* stream) {
   if (int rc = check_step_opt(L, P, o, count)) return rc;
-  if (!counter_dev || !slots_out) return fail(DQZ_ERR_INVALID, "null argument");
-  if (size < 1) return fail(DQZ_ERR_INVALID, "cannot sample from an empty replay (size=%lld)", (long long)size);
-  if (capacity < size || base < 0) return fail(DQZ_ERR_INVALID, "bad replay geometry");
-  if (L->cfg.algo == DQZ_ALGO_PER) return fail(DQZ_ERR_INVALID, "PER samples by priority, not uniformly");
-  const UniformDraw d{base % capacity, size, capacity, seed, counter_dev, slots_out};
-  if (int rc = step_impl(L, P, S, slots_out, nullptr, stream, kNoProfile, o->grad, nullptr, &d)) return rc;
+  UniformDraw d;
+  if (int rc = uniform_draw_args(L, base, size, capacity, seed, counter_dev, slots_out, &d)) return rc;
+  if (int rc = step_impl(L, P, S, {.draw = &d, .gout = o->grad}, stream)) return rc;
   return dqz_optimizer_apply(o, P->online, o->grad, P->mu, P->nu, count, stream);
 }
 
@@ -906,9 +864,8 @@ struct dqz_meta {
   float *ty1, *ty2, *ty3, *td4, *td3, *td2, *td1, *s1;
   uint8_t* x1;  // [4][84][84] the online transition's s_tm1 bytes (written by the theta' forward)
   float* dotp;  // [C][META_DOT_SLOTS] the tangent launch's dot-product partials (one chunk)
-  int* arrive;  // (x Handoff::kStride) [0] meta_adam_chunks_kernel's re-seed arrival counter, [1, 3) the
-                // HVP's ddot1 hand-off words, [3] the Adam entry counter (all zero between launches),
-                // [4] the meta-level error word (dqz_meta_sync_status)
+  int* arrive;  // kMetaWords hand-off words (layout.hpp MetaWord), read through word()
+  int* word(MetaWord w) const { return arrive + w * Handoff::kStride; }
   unsigned spin_max = 1u << 24;  // polls before the Adam leader's entry wait gives up
   int nparts2;
   void* block;
@@ -950,23 +907,20 @@ int dqz_meta_create(const dqz_meta_config* cfg, dqz_meta** out) {
   H->nparts = (int)((H->total / 4 + 255) / 256);
   H->nparts2 = (int)((H->total + 255) / 256);
   const int64_t so = cfg->second_order ? 1 : 0;
-  const int64_t sizes[] = {H->total, H->total, H->total, H->total, H->total,
-                           (int64_t)C * C1M * C1CO, (int64_t)C * C2M * C2CO, (int64_t)C * FLAT,
-                           (int64_t)H->lm->S_fc1 * C * HID,
-                           M, KC, KC, M, 1, H->nparts2, KC, KC, multi * H->total,
-                           so * H->total, so * H->total, so * H->nparts2,
-                           so * C1M * C1CO, so * C2M * C2CO, so * FLAT, so * HID, so * FLAT,
-                           so * C2M * C2CO, so * C1M * C1CO, so, so * HVP_T4_CHUNKS * HID,
-                           (int64_t)C * META_DOT_SLOTS, 5 * Handoff::kStride, so * FC * FB / 4};
-  float** ptrs[] = {&H->G, &H->thp, &H->mu1, &H->nu1, &H->J, &H->zv1, &H->zv2, &H->zv3, &H->zvp,
-                    &H->x, &H->p, &H->s, &H->dl, &H->loss, &H->loss_part, &H->td,
-                    reinterpret_cast<float**>(&H->slots_pad), &H->Gs,
-                    &H->GQ, &H->HQ, &H->s1_part,
-                    &H->ty1, &H->ty2, &H->ty3, &H->td4, &H->td3, &H->td2, &H->td1, &H->s1, &H->hpart,
-                    &H->dotp, reinterpret_cast<float**>(&H->arrive), reinterpret_cast<float**>(&H->x1)};
-  static_assert(sizeof(sizes) / sizeof(sizes[0]) == sizeof(ptrs) / sizeof(ptrs[0]), "meta scratch table");
-  int64_t tot = 0;
-  for (int64_t n : sizes) tot += (n + 63) / 64 * 64;
+  const int64_t T = H->total, np2 = H->nparts2;
+  // the scratch buffers in allocation order, sizes in floats (layout.hpp carve)
+  const Carve bufs[] = {
+      {&H->G, T}, {&H->thp, T}, {&H->mu1, T}, {&H->nu1, T}, {&H->J, T},
+      {&H->zv1, (int64_t)C * C1M * C1CO}, {&H->zv2, (int64_t)C * C2M * C2CO}, {&H->zv3, (int64_t)C * FLAT},
+      {&H->zvp, (int64_t)H->lm->S_fc1 * C * HID},
+      {&H->x, M}, {&H->p, KC}, {&H->s, KC}, {&H->dl, M}, {&H->loss, 1}, {&H->loss_part, np2}, {&H->td, KC},
+      {&H->slots_pad, KC}, {&H->Gs, multi * T},
+      {&H->GQ, so * T}, {&H->HQ, so * T}, {&H->s1_part, so * np2},
+      {&H->ty1, so * C1M * C1CO}, {&H->ty2, so * C2M * C2CO}, {&H->ty3, so * FLAT}, {&H->td4, so * HID},
+      {&H->td3, so * FLAT}, {&H->td2, so * C2M * C2CO}, {&H->td1, so * C1M * C1CO}, {&H->s1, so},
+      {&H->hpart, so * HVP_T4_CHUNKS * HID},
+      {&H->dotp, (int64_t)C * META_DOT_SLOTS}, {&H->arrive, kMetaWords * Handoff::kStride}, {&H->x1, so * FC * FB / 4}};
+  const int64_t tot = carve(bufs, nullptr);
   if (hipMalloc(&H->block, tot * sizeof(float)) != hipSuccess || hipMemset(H->block, 0, tot * sizeof(float)) != hipSuccess) {
     if (H->block) (void)hipFree(H->block);
     dqz_learner_destroy(H->lm);
@@ -974,11 +928,7 @@ int dqz_meta_create(const dqz_meta_config* cfg, dqz_meta** out) {
     delete H;
     return fail(DQZ_ERR_HIP, "hipMalloc of %lld bytes of meta scratch failed", (long long)(tot * 4));
   }
-  float* q = (float*)H->block;
-  for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) {
-    *ptrs[i] = q;
-    q += (sizes[i] + 63) / 64 * 64;
-  }
+  carve(bufs, (float*)H->block);
   *out = H;
   return DQZ_OK;
 }
@@ -992,6 +942,185 @@ int dqz_meta_destroy(dqz_meta* H) {
   return DQZ_OK;
 }
 
+// One dqz_meta_update call: the entry's arguments, then what the stages (DESIGN §4's, in its order) share.
+struct MetaRun {
+  dqz_meta* H;
+  const dqz_params* P;
+  const dqz_store *S, *S1;
+  const int32_t *slots, *online_slot, *pos;
+  float *logits, *adam_mu, *adam_nu;
+  int32_t* adam_count;
+  dqz_logit_buffer* logit_buf;
+  void* stream;
+  hipStream_t st = (hipStream_t)stream;
+  const int32_t* mslots = H->K == 1 ? slots : H->slots_pad;  // padded to K C when K > 1
+  // the meta stage the gradient epilogues apply (Rms::meta, set by each pass) and its buffers
+  Rms epi{.thp = H->thp, .mu1 = H->mu1, .nu1 = H->nu1, .J = H->J, .sq_part = H->loss_part};
+  dqz_params P1{H->thp, P->online, nullptr, nullptr};  // the theta' pass: online = theta', target = theta
+  const float* v = H->cfg.second_order ? H->thp : H->G;  // the tangent direction the theta' pass leaves
+  // the theta' pass's partial sums of u'^2 (the fc1 dW blocks', then the update's) that the Adam stage folds
+  const int A = H->cfg.num_actions;
+  int nloss = 4 * (FLAT / 16) + (int)update_blocks(H->l1->sz, A, H->l1->shared_bias ? 1 : A);
+};
+
+// G = sum_i p_i g_i, p = softmax(logits[pos]): batched backwards with p-weighted cotangents, one per chunk of C
+// samples, accumulated in chunk order (deterministic); K > 1 pads the slots to K C with slots[M - 1] (p = 0 there).
+// One chunk: no padding, the head forms p itself (MetaSoftmax), and meta_rms1 runs in the backward's gradient
+// epilogues (Rms::meta1); G itself is stored only for the second order (meta_second_kernel reads it).
+static int meta_weighted_grad(MetaRun& m) {
+  dqz_meta* H = m.H;
+  const int M = H->cfg.meta_batch, C = H->C, K = H->K;
+  if (K == 1) {
+    m.epi.meta = 1;
+    const MetaSoftmax msm{m.logits, m.pos, M, H->x, H->p};
+    // (the batch learner's td stays current until the next update, dqz_meta_outputs copies it from there)
+    return step_impl(H->lm, m.P, m.S, {.slots = m.mslots, .gout = H->cfg.second_order ? H->G : nullptr,
+                                       .meta_p = H->p, .meta_epi = &m.epi, .meta_sm = &msm}, m.stream);
+  }
+  hipLaunchKernelGGL(meta_softmax_kernel, dim3(1 + (unsigned)((K * C + META_THREADS - 1) / META_THREADS)),
+                     dim3(META_THREADS), 0, m.st, m.logits, m.pos, M, H->x, H->p, m.slots, K * C, H->slots_pad);
+  DQZ_HIP(hipGetLastError());
+  for (int64_t k = 0; k < K; ++k) {
+    if (int rc = step_impl(H->lm, m.P, m.S, {.slots = H->slots_pad + k * C, .gout = H->G, .gacc = k > 0 ? 1 : 0,
+                                             .meta_p = H->p + k * C}, m.stream))
+      return rc;
+    DQZ_HIP(hipMemcpyAsync(H->td + k * C, H->lm->td, sizeof(float) * C, hipMemcpyDeviceToDevice, m.st));
+  }
+  return DQZ_OK;
+}
+
+// K > 1: theta' = theta + u(G), mu', nu', J in a launch of its own
+static int meta_rms1(const MetaRun& m) {
+  const dqz_meta* H = m.H;
+  const MetaRmsArgs ra{.lr = H->cfg.learning_rate, .decay = H->cfg.decay, .c1 = (float)(1.0 - (double)H->cfg.decay),
+                       .eps = H->cfg.eps, .n4 = H->total / 4};
+  hipLaunchKernelGGL(meta_rms1_kernel, dim3((unsigned)((ra.n4 + 255) / 256)), dim3(256), 0, m.st, ra,
+                     (const float4*)H->G, (const float4*)m.P->online, (const float4*)m.P->mu, (const float4*)m.P->nu,
+                     (float4*)H->thp, (float4*)H->mu1, (float4*)H->nu1, (float4*)H->J);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+// theta' pass, first order: g' = grad loss_fn(theta', online transition) is consumed where it is formed by
+// meta_rms2 (Rms::meta2): v = -2 u' du/dG -> the G buffer (free in the first order), block sums of u'^2.
+static int meta_theta_first(MetaRun& m) {
+  m.epi.meta = 2;
+  m.epi.vout = m.H->G;
+  return step_impl(m.H->l1, &m.P1, m.S1, {.slots = m.online_slot, .meta_epi = &m.epi}, m.stream);
+}
+
+// theta' pass, second order: grad q[a] (unit cotangent) -> GQ, consumed where it is formed (Rms::meta3): v_dir ->
+// mu1, w -> nu1, block sums of u'^2 and grad q . w.  The one-sample learner keeps the primal activations, the
+// backward signals and td' for the HVP, whose epilogue combines v -> thp (theta' is no longer needed).
+static int meta_theta_second(MetaRun& m) {
+  dqz_meta* H = m.H;
+  dqz_learner* L1 = H->l1;
+  m.epi.meta = 3;
+  m.epi.G2 = H->G;
+  m.epi.td = L1->td;
+  m.epi.bound = H->cfg.grad_error_bound;
+  m.epi.s1_part = H->s1_part;
+  if (int rc = step_impl(L1, &m.P1, m.S1, {.slots = m.online_slot, .gout = H->GQ, .unit = 1, .meta_epi = &m.epi,
+                                           .xout = H->x1}, m.stream))
+    return rc;
+  // (vdir .. vout: meta_combine in hvp_g's epilogue, v = v_dir + J (alpha s1 grad q - clip(td') H w) -> thp)
+  HvpArgs hv{.x = H->x1, .rec = reinterpret_cast<const float4*>(L1->rec), .th = H->thp, .tw = H->nu1,
+             .A = H->cfg.num_actions, .y1 = L1->y1, .y2 = L1->y2, .y3 = L1->y3, .h = L1->h1,
+             .d1 = L1->dy1, .d2 = L1->dy2, .d3 = L1->dy3, .d4 = L1->dz1,
+             .ty1 = H->ty1, .ty2 = H->ty2, .ty3 = H->ty3, .td4 = H->td4, .td3 = H->td3, .td2 = H->td2, .td1 = H->td1,
+             .hq = H->HQ, .part = H->hpart, .s1_part = H->s1_part, .s1_nparts = m.nloss, .s1 = H->s1,
+             .vdir = H->mu1, .J = H->J, .gq = H->GQ, .td = L1->td, .bound = H->cfg.grad_error_bound, .vout = H->thp};
+  for (int i = 0; i < 10; ++i) hv.off[i] = L1->off[i];
+  // ddot1's in-launch hand-off; a timeout lands in the one-transition learner's error word
+  hv.td1_pub = Handoff{H->word(kMetaDdot1Cnt), H->word(kMetaDdot1Ack), L1->sync + sync_of(L1).err(), HVP_B1, HVP_G_C1,
+                       L1->spin_max};
+  // three launches (hvp.hpp): the tangent forward and backward side by side, then the parameter blocks of H_q w
+  hipLaunchKernelGGL(hvp_l1_kernel, dim3(HVP_L1_BLOCKS), dim3(256), 0, m.st, hv);
+  hipLaunchKernelGGL(hvp_l2_kernel, dim3(HVP_L2_BLOCKS), dim3(256), 0, m.st, hv);
+  hipLaunchKernelGGL(hvp_l3_kernel, dim3(HVP_L3_BLOCKS), dim3(256), 0, m.st, hv);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+// Tangent forward arguments (V * y + vb per layer, no ReLU) over the batch learner's activations, chunk at `ks`
+static FwdArgs tangent_args(const MetaRun& m, const int32_t* ks) {
+  const dqz_meta* H = m.H;
+  const NetZ nv{{m.v, m.v, m.v}, {0, 0, 0}};
+  FwdArgs t = make_fwd_args(H->lm, nv, 1, H->C, Conv1Src{m.S->frames, m.S->fidx, ks, nullptr, 0, UniformDraw{}});
+  t.c1.linear = t.c2.linear = t.c3.linear = 1;
+  t.c1.out = H->zv1;
+  t.c2.out = H->zv2;
+  t.c3.out = H->zv3;
+  t.f1.part = H->zvp;
+  return t;
+}
+
+// Tangent stage, one chunk (the batch learner still holds the first pass's activations and backward signals): the
+// conv layers' dot products from the per-sample gradient slabs beside the fc1 tangent range (meta.hpp SlabDotArgs).
+static int meta_tangent_one(const MetaRun& m) {
+  const dqz_meta* H = m.H;
+  const dqz_learner* L = H->lm;
+  FwdArgs t = tangent_args(m, m.mslots);
+  t.f1.dot = TangentDot{L->dz1, H->dotp, 12};
+  const MetaExtra ex{L->dz1, L->h1, L->gq, L->ga, m.v, L->off[7], L->off[8], L->off[9], H->cfg.num_actions, H->dotp};
+  const SlabDotArgs sd{.p1 = L->p1, .p2 = L->p2, .p3 = L->p3, .v = m.v, .off1 = L->off[0], .off2 = L->off[2],
+                       .off3 = L->off[4], .part = H->dotp, .M = H->C};
+  hipLaunchKernelGGL(tangent_slab_kernel, dim3((unsigned)tangent_slab_blocks(H->C, t.f1.MG)), dim3(256), 0, m.st, sd,
+                     t.f1, ex);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+// Tangent stage, K > 1, chunk by chunk: the chunk's forward / backward is recomputed so the batch learner holds its
+// activations and backward signals, then the four layers' tangent outputs (one launch) and their dot products -> s.
+static int meta_tangent_chunks(const MetaRun& m) {
+  const dqz_meta* H = m.H;
+  dqz_learner* L = H->lm;
+  const int C = H->C;
+  for (int64_t k = 0; k < H->K; ++k) {
+    const int32_t* ks = m.mslots + k * C;
+    if (int rc = step_impl(L, m.P, m.S, {.slots = ks, .gout = H->Gs, .meta_p = H->p + k * C}, m.stream)) return rc;
+    const FwdArgs t = tangent_args(m, ks);
+    hipLaunchKernelGGL(tangent_fwd_kernel, dim3((unsigned)tangent_fwd_blocks(C, t.f1.MG)), dim3(256), kConv1FwdSmem,
+                       m.st, t.c1, t.c2, t.c3, t.f1, MetaExtra{});
+    DQZ_HIP(hipGetLastError());
+    const MetaDotArgs md{.dy1 = L->dy1, .dy2 = L->dy2, .dy3 = L->dy3, .dz1 = L->dz1, .gq = L->gq, .ga = L->ga,
+                         .zv1 = H->zv1, .zv2 = H->zv2, .zv3 = H->zv3, .zvp = H->zvp, .S = FC1_S, .M = C,
+                         .A = H->cfg.num_actions, .v = m.v, .b1_off = L->off[7], .w2_off = L->off[8],
+                         .b2_off = L->off[9], .h1 = L->h1, .s_out = H->s + k * C};
+    hipLaunchKernelGGL(meta_dot_kernel, dim3(C), dim3(256), 0, m.st, md);
+    DQZ_HIP(hipGetLastError());
+  }
+  return DQZ_OK;
+}
+
+// Adam on the M logits from s (K > 1) or the tangent launch's partials
+static int meta_adam(const MetaRun& m) {
+  const dqz_meta* H = m.H;
+  dqz_logit_buffer* buf = m.logit_buf;
+  // keep the buffer's running log-sum-exp current (the host keeps vouching for it: every write went through here)
+  const bool keep = buf && buf->run_known;
+  const MetaAdamArgs ad{.x = H->x, .p = H->p, .s = H->s, .dot_part = H->K == 1 ? H->dotp : nullptr, .s_out = H->s,
+                        .M = H->cfg.meta_batch, .logits = m.logits, .pos = m.pos, .m = m.adam_mu, .v = m.adam_nu,
+                        .count = m.adam_count, .lr = H->cfg.meta_learning_rate, .b1 = H->cfg.b1, .b2 = H->cfg.b2,
+                        .eps = H->cfg.meta_eps, .loss_part = H->loss_part, .nparts = m.nloss, .loss = H->loss,
+                        .dlogits = H->dl, .run = keep ? buf->run : nullptr, .dirty = keep ? buf->dirty : nullptr,
+                        .n_logits = keep ? buf->capacity : 0};
+  // (the fused form's re-seed path addresses the buffer with 32-bit byte offsets)
+  if (keep && H->K == 1 && ad.M <= META_THREADS && buf->capacity * 4 <= INT32_MAX) {
+    // Adam and the re-sums of the chunks it writes in one launch
+    MetaAdamChunks ck{buf->csum, buf->nblocks, H->word(kMetaReseed), H->word(kMetaAdamEntry), H->word(kMetaErr),
+                      H->spin_max};
+    hipLaunchKernelGGL(meta_adam_chunks_kernel, dim3(buf->nblocks), dim3(META_THREADS), 0, m.st, ad, ck);
+    DQZ_HIP(hipGetLastError());
+    return DQZ_OK;
+  }
+  hipLaunchKernelGGL(meta_adam_kernel, dim3(1), dim3(META_THREADS), 0, m.st, ad);
+  DQZ_HIP(hipGetLastError());
+  if (keep) return chunk_sums(buf, m.logits, true, m.st);
+  return DQZ_OK;
+}
+
 int dqz_meta_update(dqz_meta* H, const dqz_params* P, const dqz_store* S, const int32_t* slots,
                     const dqz_store* S1, const int32_t* online_slot, float* logits, const int32_t* pos,
                     float* adam_mu, float* adam_nu, int32_t* adam_count, dqz_logit_buffer* logit_buf,
@@ -1001,288 +1130,16 @@ int dqz_meta_update(dqz_meta* H, const dqz_params* P, const dqz_store* S, const 
     return fail(DQZ_ERR_INVALID, "null argument");
   if (int rc = check_store(S)) return rc;
   if (int rc = check_store(S1)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  dqz_learner* L = H->lm;
-  const int M = H->cfg.meta_batch, A = H->cfg.num_actions;
-
-  const int C = H->C, K = H->K;
-
-  // p = softmax(logits[pos]); slots padded to K C with slots[M - 1] (p = 0
-  // there).  One chunk (K C = M): no padding, and the batch learner's head
-  // forms p itself (HeadArgs::meta_logits), so no launch of its own.
-  const int32_t* mslots = K == 1 ? slots : H->slots_pad;
-  if (K > 1) {
-    hipLaunchKernelGGL(meta_softmax_kernel, dim3(1 + (unsigned)((K * C + META_THREADS - 1) / META_THREADS)),
-                       dim3(META_THREADS), 0, st, logits, pos, M, H->x, H->p, slots, K * C, H->slots_pad);
-    DQZ_HIP(hipGetLastError());
-  }
-
-  // G = sum_i p_i g_i: batched backwards with p-weighted cotangents, one per
-  // chunk of C samples, accumulated in chunk order (deterministic).  With one
-  // chunk, meta_rms1 (theta' = theta + u(G), mu', nu', J) runs in the
-  // backward's gradient epilogues (Rms::meta1) instead of its own launch; G
-  // itself is stored only for the second order (meta_second_kernel reads it).
-  const bool so = H->cfg.second_order != 0;
-  Rms epi{};
-  epi.thp = H->thp;
-  epi.mu1 = H->mu1;
-  epi.nu1 = H->nu1;
-  epi.J = H->J;
-  epi.sq_part = H->loss_part;
-  if (K == 1) {
-    epi.meta = 1;
-    HeadArgs msm{};
-    msm.meta_logits = logits;
-    msm.meta_pos = pos;
-    msm.meta_M = M;
-    msm.meta_x_out = H->x;
-    msm.meta_p_out = H->p;
-    if (int rc = step_impl(L, P, S, mslots, nullptr, stream, kNoProfile, so ? H->G : nullptr, H->p, nullptr, 0, 0,
-                           nullptr, nullptr, nullptr, &epi, &msm))
-      return rc;
-    // (the batch learner's td stays current until the next update,
-    // dqz_meta_outputs copies it from there)
-  } else {
-    for (int k = 0; k < K; ++k) {
-      if (int rc = step_impl(L, P, S, H->slots_pad + (int64_t)k * C, nullptr, stream, kNoProfile, H->G,
-                             H->p + (int64_t)k * C, nullptr, 0, k > 0 ? 1 : 0))
-        return rc;
-      DQZ_HIP(hipMemcpyAsync(H->td + (int64_t)k * C, L->td, sizeof(float) * C, hipMemcpyDeviceToDevice, st));
-    }
-  }
-
-  MetaRmsArgs ra{};
-  ra.lr = H->cfg.learning_rate;
-  ra.decay = H->cfg.decay;
-  ra.c1 = (float)(1.0 - (double)H->cfg.decay);
-  ra.eps = H->cfg.eps;
-  ra.n4 = H->total / 4;
-  const dim3 eg((unsigned)((ra.n4 + 255) / 256));
-  if (K > 1) {
-    hipLaunchKernelGGL(meta_rms1_kernel, eg, dim3(256), 0, st, ra, (const float4*)H->G, (const float4*)P->online,
-                       (const float4*)P->mu, (const float4*)P->nu, (float4*)H->thp, (float4*)H->mu1,
-                       (float4*)H->nu1, (float4*)H->J);
-    DQZ_HIP(hipGetLastError());
-  }
-
-  dqz_params P1;
-  P1.online = H->thp;
-  P1.target = P->online;
-  P1.mu = nullptr;
-  P1.nu = nullptr;
-  int nloss = H->nparts;
-  const float* v = H->thp;
-  if (!so) {
-    // g' = grad loss_fn(theta', target = theta, online transition), consumed
-    // where it is formed by meta_rms2 (Rms::meta2): v = -2 u' du/dG -> the G
-    // buffer (free in the first order), per-block partial sums of u'^2 (the
-    // fc1 dW blocks' then the update's).
-    epi.meta = 2;
-    epi.vout = H->G;
-    if (int rc = step_impl(H->l1, &P1, S1, online_slot, nullptr, stream, kNoProfile, nullptr, nullptr, nullptr, 0, 0,
-                           nullptr, nullptr, nullptr, &epi))
-      return rc;
-    v = H->G;
-    nloss = 4 * (FLAT / 16) + (int)update_blocks(H->l1->sz, A, H->l1->shared_bias ? 1 : A);
-  } else {
-    // grad q[a] at theta' (unit cotangent) -> GQ; the one-sample learner keeps
-    // the primal activations, the unit-cotangent backward signals and td'.
-    dqz_learner* L1 = H->l1;
-    // ... consumed where it is formed (Rms::meta3, meta_second_kernel's
-    // stage): v_dir -> mu1, w -> nu1, block sums of u'^2 and grad q . w
-    epi.meta = 3;
-    epi.G2 = H->G;
-    epi.td = L1->td;
-    epi.bound = H->cfg.grad_error_bound;
-    epi.s1_part = H->s1_part;
-    if (int rc = step_impl(L1, &P1, S1, online_slot, nullptr, stream, kNoProfile, H->GQ, nullptr, nullptr, 1, 0,
-                           nullptr, nullptr, nullptr, &epi, nullptr, H->x1))
-      return rc;
-    const int nparts1 = 4 * (FLAT / 16) + (int)update_blocks(L1->sz, A, L1->shared_bias ? 1 : A);
-    HvpArgs hv{};
-    hv.x = H->x1;
-    hv.rec = reinterpret_cast<const float4*>(L1->rec);
-    hv.th = H->thp;
-    hv.tw = H->nu1;
-    for (int i = 0; i < 10; ++i) hv.off[i] = L1->off[i];
-    hv.A = A;
-    hv.y1 = L1->y1;
-    hv.y2 = L1->y2;
-    hv.y3 = L1->y3;
-    hv.h = L1->h1;
-    hv.d1 = L1->dy1;
-    hv.d2 = L1->dy2;
-    hv.d3 = L1->dy3;
-    hv.d4 = L1->dz1;
-    hv.ty1 = H->ty1;
-    hv.ty2 = H->ty2;
-    hv.ty3 = H->ty3;
-    hv.td4 = H->td4;
-    hv.td3 = H->td3;
-    hv.td2 = H->td2;
-    hv.td1 = H->td1;
-    hv.hq = H->HQ;
-    hv.part = H->hpart;
-    hv.s1_part = H->s1_part;
-    hv.s1_nparts = nparts1;
-    hv.s1 = H->s1;
-    // meta_combine in hvp_g's epilogue: v = v_dir + J (alpha s1 grad q -
-    // clip(td') H w) -> thp (theta' is no longer needed)
-    hv.vdir = H->mu1;
-    hv.J = H->J;
-    hv.gq = H->GQ;
-    hv.td = L1->td;
-    hv.bound = H->cfg.grad_error_bound;
-    hv.vout = H->thp;
-    // ddot1's in-launch hand-off: words after the Adam re-seed counter, the
-    // one-transition learner's error word (dqz_learner_sync_status)
-    hv.td1_pub = Handoff{H->arrive + Handoff::kStride, H->arrive + 2 * Handoff::kStride,
-                         L1->sync + 16 * Handoff::kStride, HVP_B1, HVP_G_C1, L1->spin_max};
-    // three launches (hvp.hpp): the tangent forward and backward side by
-    // side, then the parameter blocks of H_q w
-    hipLaunchKernelGGL(hvp_l1_kernel, dim3(HVP_L1_BLOCKS), dim3(256), 0, st, hv);
-    hipLaunchKernelGGL(hvp_l2_kernel, dim3(HVP_L2_BLOCKS), dim3(256), 0, st, hv);
-    hipLaunchKernelGGL(hvp_l3_kernel, dim3(HVP_L3_BLOCKS), dim3(256), 0, st, hv);
-    DQZ_HIP(hipGetLastError());
-    nloss = nparts1;
-  }
-
-  // Tangent forward over the stored online activations: V * y + vb per layer,
-  // chunk by chunk (K > 1: the chunk's forward / backward is recomputed first
-  // so L holds its activations and p-weighted backward signals).
-  NetZ nv{};
-  nv.p[0] = nv.p[1] = nv.p[2] = v;
-  nv.which[0] = nv.which[1] = nv.which[2] = 0;
-  for (int k = 0; k < K; ++k) {
-    const int32_t* ks = mslots + (int64_t)k * C;
-    if (K > 1) {
-      if (int rc = step_impl(L, P, S, ks, nullptr, stream, kNoProfile, H->Gs, H->p + (int64_t)k * C)) return rc;
-    }
-    Conv1FwdArgs c1{};
-    c1.src = Conv1Src{S->frames, S->fidx, ks, nullptr, 0, UniformDraw{}};
-    c1.nz = nv;
-    c1.w_off = L->off[0];
-    c1.b_off = L->off[1];
-    c1.B = C;
-    c1.Z = 1;
-    c1.linear = 1;
-    c1.out = H->zv1;
-    LayerFwdArgs c2{};
-    c2.in = L->y1;
-    c2.nz = nv;
-    c2.w_off = L->off[2];
-    c2.b_off = L->off[3];
-    c2.B = C;
-    c2.Z = 1;
-    c2.linear = 1;
-    c2.out = H->zv2;
-    LayerFwdArgs c3 = c2;
-    c3.in = L->y2;
-    c3.w_off = L->off[4];
-    c3.b_off = L->off[5];
-    c3.out = H->zv3;
-    Fc1FwdArgs f1{};
-    f1.in = L->y3;
-    f1.nz = nv;
-    f1.w_off = L->off[6];
-    f1.B = C;
-    f1.MG = (C + 31) / 32;
-    f1.part = H->zvp;
-    MetaExtra ex{};
-    if (K == 1) {  // dot products in the tangent epilogues (meta.hpp)
-      c1.dot = TangentDot{L->dy1, H->dotp, 0};
-      c2.dot = TangentDot{L->dy2, H->dotp, 4};
-      c3.dot = TangentDot{L->dy3, H->dotp, 8};
-      f1.dot = TangentDot{L->dz1, H->dotp, 12};
-      ex = MetaExtra{L->dz1, L->h1, L->gq, L->ga, v, L->off[7], L->off[8], L->off[9], A, H->dotp};
-    }
-    if (K == 1) {
-      // the conv layers' dot products from the batch backward's per-sample
-      // gradient slabs, beside the fc1 tangent range (meta.hpp SlabDotArgs)
-      SlabDotArgs sd{};
-      sd.p1 = L->p1;
-      sd.p2 = L->p2;
-      sd.p3 = L->p3;
-      sd.v = v;
-      sd.off1 = L->off[0];
-      sd.off2 = L->off[2];
-      sd.off3 = L->off[4];
-      sd.part = H->dotp;
-      sd.M = C;
-      hipLaunchKernelGGL(tangent_slab_kernel, dim3((unsigned)tangent_slab_blocks(C, f1.MG)), dim3(256), 0, st, sd,
-                         f1, ex);
-      DQZ_HIP(hipGetLastError());
-      break;
-    }
-    // the four layers' tangent outputs are independent: one launch
-    hipLaunchKernelGGL(tangent_fwd_kernel, dim3((unsigned)tangent_fwd_blocks(C, f1.MG)), dim3(256), kConv1FwdSmem,
-                       st, c1, c2, c3, f1, ex);
-    DQZ_HIP(hipGetLastError());
-    if (K == 1) break;
-
-    MetaDotArgs md{};
-    md.dy1 = L->dy1;
-    md.dy2 = L->dy2;
-    md.dy3 = L->dy3;
-    md.dz1 = L->dz1;
-    md.gq = L->gq;
-    md.ga = L->ga;
-    md.zv1 = H->zv1;
-    md.zv2 = H->zv2;
-    md.zv3 = H->zv3;
-    md.zvp = H->zvp;
-    md.S = FC1_S;
-    md.M = C;
-    md.A = A;
-    md.v = v;
-    md.b1_off = L->off[7];
-    md.w2_off = L->off[8];
-    md.b2_off = L->off[9];
-    md.h1 = L->h1;
-    md.s_out = H->s + (int64_t)k * C;
-    hipLaunchKernelGGL(meta_dot_kernel, dim3(C), dim3(256), 0, st, md);
-    DQZ_HIP(hipGetLastError());
-  }
-
-  MetaAdamArgs ad{};
-  ad.x = H->x;
-  ad.p = H->p;
-  ad.s = H->s;
-  ad.dot_part = K == 1 ? H->dotp : nullptr;
-  ad.s_out = H->s;
-  ad.M = M;
-  ad.logits = logits;
-  ad.pos = pos;
-  ad.m = adam_mu;
-  ad.v = adam_nu;
-  ad.count = adam_count;
-  ad.lr = H->cfg.meta_learning_rate;
-  ad.b1 = H->cfg.b1;
-  ad.b2 = H->cfg.b2;
-  ad.eps = H->cfg.meta_eps;
-  ad.loss_part = H->loss_part;
-  ad.nparts = nloss;
-  ad.loss = H->loss;
-  ad.dlogits = H->dl;
-  // keep the buffer's running log-sum-exp current (the host keeps vouching
-  // for it: every write went through the library)
-  const bool keep = logit_buf && logit_buf->run_known;
-  ad.run = keep ? logit_buf->run : nullptr;
-  ad.dirty = keep ? logit_buf->dirty : nullptr;
-  ad.n_logits = keep ? logit_buf->capacity : 0;
-  // (the fused form's re-seed path addresses the buffer with 32-bit byte offsets)
-  if (keep && K == 1 && M <= META_THREADS && logit_buf->capacity * 4 <= INT32_MAX) {
-    // Adam and the re-sums of the chunks it writes in one launch
-    MetaAdamChunks ck{logit_buf->csum, logit_buf->nblocks, H->arrive, H->arrive + 3 * Handoff::kStride,
-                      H->arrive + 4 * Handoff::kStride, H->spin_max};
-    hipLaunchKernelGGL(meta_adam_chunks_kernel, dim3(logit_buf->nblocks), dim3(META_THREADS), 0, st, ad, ck);
-    DQZ_HIP(hipGetLastError());
-    return DQZ_OK;
-  }
-  hipLaunchKernelGGL(meta_adam_kernel, dim3(1), dim3(META_THREADS), 0, st, ad);
-  DQZ_HIP(hipGetLastError());
-  if (keep) return chunk_sums(logit_buf, logits, true, st);
-  return DQZ_OK;
+  MetaRun m{.H = H, .P = P, .S = S, .S1 = S1, .slots = slots, .online_slot = online_slot, .pos = pos,
+            .logits = logits, .adam_mu = adam_mu, .adam_nu = adam_nu, .adam_count = adam_count,
+            .logit_buf = logit_buf, .stream = stream};
+  const bool one = H->K == 1;
+  if (int rc = meta_weighted_grad(m)) return rc;
+  if (!one)
+    if (int rc = meta_rms1(m)) return rc;
+  if (int rc = H->cfg.second_order ? meta_theta_second(m) : meta_theta_first(m)) return rc;
+  if (int rc = one ? meta_tangent_one(m) : meta_tangent_chunks(m)) return rc;
+  return meta_adam(m);
 }
 
 int dqz_meta_sync_status(dqz_meta* H, int* status) {
@@ -1291,16 +1148,16 @@ int dqz_meta_sync_status(dqz_meta* H, int* status) {
   // (each learner's check clears that learner's words when its word is set)
   if (int rc = dqz_learner_sync_status(H->lm, &s_lm)) return rc;
   if (int rc = dqz_learner_sync_status(H->l1, &s_l1)) return rc;
-  DQZ_HIP(hipMemcpy(&s_own, H->arrive + 4 * Handoff::kStride, sizeof(int), hipMemcpyDeviceToHost));
+  DQZ_HIP(hipMemcpy(&s_own, H->word(kMetaErr), sizeof(int), hipMemcpyDeviceToHost));
   *status = s_lm | s_l1 | s_own;
   if (*status != 0) {
     // a wait gave up somewhere in the meta-update: late arrivals may have
     // left counts behind after a reset, so clear every word the meta handle
     // owns (its learners' words are cleared just above only when their own
     // word is set: the HVP's ddot1 timeout lands in l1's word)
-    DQZ_HIP(hipMemset(H->arrive, 0, sizeof(int) * 5 * Handoff::kStride));
+    DQZ_HIP(hipMemset(H->arrive, 0, sizeof(int) * kMetaWords * Handoff::kStride));
     for (dqz_learner* L : {H->lm, H->l1})
-      DQZ_HIP(hipMemset(L->sync, 0, sizeof(int) * ((16 * L->cfg.batch + 3) * Handoff::kStride + 64)));
+      DQZ_HIP(hipMemset(L->sync, 0, sizeof(int) * sync_of(L).ints()));
     DQZ_HIP(hipDeviceSynchronize());
   }
   return DQZ_OK;
@@ -1315,8 +1172,8 @@ int dqz_meta_debug_stall(dqz_meta* H, int poison, unsigned spin_max) {
   if (poison) {
     const int32_t p = -(1 << 30);
     DQZ_HIP(hipDeviceSynchronize());
-    DQZ_HIP(hipMemcpy(H->arrive + Handoff::kStride, &p, sizeof(p), hipMemcpyHostToDevice));      // ddot1 cnt
-    DQZ_HIP(hipMemcpy(H->arrive + 3 * Handoff::kStride, &p, sizeof(p), hipMemcpyHostToDevice));  // Adam entry
+    DQZ_HIP(hipMemcpy(H->word(kMetaDdot1Cnt), &p, sizeof(p), hipMemcpyHostToDevice));
+    DQZ_HIP(hipMemcpy(H->word(kMetaAdamEntry), &p, sizeof(p), hipMemcpyHostToDevice));
   }
   return DQZ_OK;
 }

@@ -1,7 +1,9 @@
 // learner_impl.hpp — host-side internals shared by libdqz's two translation
 // units (common.hpp, "Two translation units, two code objects"): the learner
-// handle, its parameter layout, argument checks, and the learner step's entry
-// (step_impl, defined in learner_step.hip) that the MGSC meta-update and the
+// handle, its parameter layout and hand-off words (layout.hpp), argument
+// checks and the builders of the fused draws' kernel arguments, the forward's
+// argument builder, and the learner step's request (StepRequest) and entry
+// (step_impl; its two halves are learner_step.hip's) that the MGSC meta-update and the
 // fused samplers in learner.hip call.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,6 +11,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "layout.hpp"
 #include "conv1.hpp"
 #include "fwd.hpp"
 #include "head.hpp"
@@ -40,14 +43,22 @@ struct dqz_learner {
   float *w3p, *w2p;  // dX-ordered weight copies written by fc1_dx_kernel each step
   double* per_wb;    // [B] the fused PER draw's unnormalised IS weights (conv1 -> head)
   int32_t* ga;
-  int32_t* sync;  // hand-off words (x Handoff::kStride): dy2 cnt/ack [B] each, fwd y1/y2 cnt/ack [3B] each,
-                  // dy1 cnt/ack [B] each, then the error word (dqz_learner_sync_status)
+  int32_t* sync;  // hand-off words and the error word: read them through sync_of / handoff (below)
   unsigned spin_max = 1u << 24;  // hand-off polls before a wait gives up
   void* block;
 };
 
-
 namespace dqz {
+
+static_assert(Handoff::kStride == kWordStride, "layout.hpp's word stride is Handoff's");
+
+// dqz_learner::sync by name (layout.hpp): the layout, and one of its hand-offs as the kernels' argument
+inline SyncLayout sync_of(const dqz_learner* L) { return SyncLayout{L->cfg.batch}; }
+inline Handoff handoff(const dqz_learner* L, const HandoffWords& w) {
+  Handoff h{L->sync + w.cnt, L->sync + w.ack, L->sync + sync_of(L).err(), w.need, w.consumers};
+  if (w.learner_spin) h.spin_max = L->spin_max;  // dqz_learner_debug_stall shortens the backward's waits only
+  return h;
+}
 
 inline int check_store(const dqz_store* S) {
   if (!S || !S->frames || !S->fidx || !S->action || !S->reward || !S->discount)
@@ -91,16 +102,103 @@ struct PhaseEvents {
   float* ms;
   bool on() const { return ms != nullptr; }
 };
-inline const PhaseEvents kNoProfile{nullptr, nullptr, 0, nullptr};
 
+inline int tree_levels(int64_t cap) {
+  int l = 0;
+  while ((int64_t(1) << l) < cap) ++l;
+  return l;
+}
 
-// One learner step (learner_step.hip; the arguments are documented there).
-int step_impl(dqz_learner* L, const dqz_params* P, const dqz_store* S, const int32_t* slots,
-              const float* is_weights, void* stream, PhaseEvents pe, float* gout = nullptr,
-              const float* meta_p = nullptr, const UniformDraw* draw = nullptr, int unit = 0,
-              int gacc = 0, const PerWbArgs* wb = nullptr, const SoftmaxDraw* sm = nullptr,
-              const PerSampleArgs* pd = nullptr, const Rms* meta_epi = nullptr,
-              const HeadArgs* meta_sm = nullptr, uint8_t* xout = nullptr,
-              const SoftmaxDrawExact* smx = nullptr);
+// The in-launch uniform draw's checks (L may be null: the step refuses that itself), then *d.
+inline int uniform_draw_args(const dqz_learner* L, int64_t base, int64_t size, int64_t capacity, uint64_t seed,
+                             uint64_t* counter_dev, int32_t* slots_out, UniformDraw* d) {
+  if (!counter_dev || !slots_out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (size < 1) return fail(DQZ_ERR_INVALID, "cannot sample from an empty replay (size=%lld)", (long long)size);
+  if (capacity < size || base < 0) return fail(DQZ_ERR_INVALID, "bad replay geometry");
+  if (L && L->cfg.algo == DQZ_ALGO_PER) return fail(DQZ_ERR_INVALID, "PER samples by priority, not uniformly");
+  *d = UniformDraw{base % capacity, size, capacity, seed, counter_dev, slots_out};
+  return DQZ_OK;
+}
+
+// The PER write-back fused into the backward launch (one wave: batch <= 64, at most PWB_LEVELS tree levels):
+// fills *wb (the step sets td and n) and says whether the geometry fits; the callers word their own refusals.
+inline bool per_wb_args(const dqz_learner* L, double* tree, int64_t cap, const int32_t* indices, double alpha,
+                        double* max_seen_dev, PerWbArgs* wb) {
+  *wb = PerWbArgs{tree, cap, tree_levels(cap), indices, nullptr, alpha, 0, max_seen_dev};
+  return L->cfg.batch <= 64 && wb->levels <= PWB_LEVELS;
+}
+
+// conv1 .. fc1 forward arguments of Z network copies on L's activations: every layer field.  forward_impl adds
+// the in-launch hand-offs; the MGSC tangent stage overrides linear, out, part and dot.
+struct FwdArgs {
+  Conv1FwdArgs c1;
+  LayerFwdArgs c2, c3;
+  Fc1FwdArgs f1;
+};
+inline FwdArgs make_fwd_args(const dqz_learner* L, const NetZ& nz, int Z, int B, const Conv1Src& src) {
+  FwdArgs a{};
+  a.c1.src = src;
+  a.c1.nz = a.c2.nz = a.f1.nz = nz;
+  a.c1.w_off = L->off[0];
+  a.c1.b_off = L->off[1];
+  a.c1.B = a.c2.B = a.f1.B = B;
+  a.c1.Z = a.c2.Z = Z;
+  a.c2.in = a.c1.out = L->y1;
+  a.c2.w_off = L->off[2];
+  a.c2.b_off = L->off[3];
+  a.c2.out = L->y2;
+  a.c3 = a.c2;
+  a.c3.in = L->y2;
+  a.c3.w_off = L->off[4];
+  a.c3.b_off = L->off[5];
+  a.f1.in = a.c3.out = L->y3;
+  a.f1.w_off = L->off[6];
+  a.f1.MG = (B + 31) / 32;
+  a.f1.part = L->fc1p;
+  return a;
+}
+
+// The meta batch's softmax formed by the batch learner's head (one meta chunk; HeadArgs::meta_logits):
+// p = softmax(logits[pos[0..M)]), block b writes x_out[b] = logits[pos[b]] and p_out[b].
+struct MetaSoftmax {
+  const float* logits;
+  const int32_t* pos;
+  int M;
+  float *x_out, *p_out;
+};
+
+// What one learner step is asked to do, set by name ({.slots = ..., .gout = ...}).  Everything left out is the
+// plain step: centered RMSProp on P->online / mu / nu over the batch `slots`.
+struct StepRequest {
+  // The batch: `slots` [B], or exactly one in-launch draw (more are refused): conv1 draws the batch itself and
+  // publishes the slots to the draw's own output, which the later kernels read; the head advances its counter.
+  const int32_t* slots;
+  const float* is_weights;      // [B] PER importance weights when the batch comes as `slots`
+  const UniformDraw* draw;      // uniform over the live window (dqz_learner_step_uniform)
+  const SoftmaxDraw* sm;        // learned logits, running state (dqz_learner_step_logits)
+  const SoftmaxDrawExact* smx;  // learned logits, numpy-exact (dqz_learner_step_logits_exact)
+  const PerSampleArgs* pd;      // prioritized: the head also forms the IS weights (dqz_learner_step_per_draw)
+  // Gradient mode: the full gradient is written to gout (dqz parameter layout; gacc = 1 adds into it: meta-batch
+  // chunks) and P->online / mu / nu are left untouched.
+  float* gout;
+  int gacc;
+  const PerWbArgs* wb;  // the PER priority write-back fused into the backward launch (per_wb_args)
+  // MGSC meta mode (dqz_meta_update)
+  const float* meta_p;         // [B] per-sample cotangents p_b * (-clip(td_b))
+  int unit;                    // 1: unit cotangent on q[a] (the HVP's pass)
+  const Rms* meta_epi;         // a meta stage applied in the gradient epilogues (Rms::meta, its buffers)
+  const MetaSoftmax* meta_sm;  // the head forms p itself; meta_p is then its p_out
+  uint8_t* xout;               // conv1 copies sample 0's s_tm1 bytes here (Conv1Src::xout)
+  PhaseEvents pe;              // dqz_learner_profile: per-phase timing instead of one pass
+};
+
+// One learner step (learner_step.hip): check_step, what a step checks before anything is enqueued, then
+// step_enqueue, its launches.  A caller with launches of its own in front runs the two halves itself.
+int check_step(const dqz_learner* L, const dqz_params* P, const dqz_store* S, const StepRequest& r);
+int step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, const StepRequest& r, void* stream);
+inline int step_impl(dqz_learner* L, const dqz_params* P, const dqz_store* S, const StepRequest& r, void* stream) {
+  if (int rc = check_step(L, P, S, r)) return rc;
+  return step_enqueue(L, P, S, r, stream);
+}
 
 }  // namespace dqz

@@ -12,6 +12,9 @@
 //     conv2 dX -> conv1 dW hand-offs, fc1 dW + fused RMSProp, conv3 / conv2
 //     dW partials                                                 bwd.hpp
 //   7 reduce of every cross-sample / split-K gradient + centered RMSProp
+// What a step is asked to do (batch source, gradient mode, PER write-back,
+// MGSC meta mode, profiling) is a StepRequest (learner_impl.hpp), whose fields
+// carry the modes' documentation; the hand-off words are named in layout.hpp.
 #define DQZ_STEP_TU 1
 #include <hip/hip_runtime.h>
 
@@ -56,26 +59,18 @@ int dqz_learner_create(const dqz_learner_config* cfg, dqz_learner** out) {
   L->Z = cfg->algo == DQZ_ALGO_DQN ? 2 : 3;
   L->shared_bias = cfg->algo == DQZ_ALGO_DQN ? 0 : 1;
   param_layout(cfg->num_actions, L->shared_bias, L->off, L->sz, &L->total);
-  const int B = cfg->batch, Z = L->Z, A = cfg->num_actions;
+  const int64_t B = cfg->batch, Z = L->Z, A = cfg->num_actions;
   L->S_fc1 = FC1_S;
-  L->S2 = B;  // per-sample conv2 dW partials (conv2_bwd_kernel)
-  L->S3 = B;  // per-sample conv3 dW partials (conv3_bwd_kernel)
-  const int64_t n_y1 = (int64_t)Z * B * C1M * C1CO, n_y2 = (int64_t)Z * B * C2M * C2CO, n_y3 = (int64_t)Z * B * FLAT;
-  const int64_t n_fc1p = (int64_t)Z * L->S_fc1 * B * HID, n_h1 = (int64_t)Z * B * HID, n_q = (int64_t)Z * B * A;
-  const int64_t n_dz1 = (int64_t)B * HID, n_dy3 = (int64_t)B * FLAT, n_dy2 = (int64_t)B * C2M * C2CO,
-                n_dy1 = (int64_t)B * C1M * C1CO;
-  const int64_t n_p1 = (int64_t)B * C1_BLOCKS * (C1KK + 1) * C1CO, n_p2 = (int64_t)L->S2 * (C2KK + 1) * C2CO,
-                n_p3 = (int64_t)L->S3 * (C3KK + 1) * C3CO;
-  const int64_t sizes[] = {n_y1, n_y2, n_y3, n_fc1p, n_h1, n_q, n_dz1, n_dy3, n_dy2, n_dy1,
-                           n_p1, n_p2, n_p3, B,      1,    B,   B,     B,  4 * B, (16 * B + 3) * Handoff::kStride + 64, W3P_N, W2P_N,
-                           2 * (int64_t)B};
-  float** ptrs[] = {&L->y1,  &L->y2,  &L->y3,  &L->fc1p, &L->h1,   &L->q,         &L->dz1, &L->dy3,
-                    &L->dy2, &L->dy1, &L->p1,  &L->p2,   &L->p3,   &L->td,        &L->loss, &L->loss_part,
-                    &L->gq,  reinterpret_cast<float**>(&L->ga), &L->rec, reinterpret_cast<float**>(&L->sync), &L->w3p, &L->w2p,
-                    reinterpret_cast<float**>(&L->per_wb)};
-  static_assert(sizeof(sizes) / sizeof(sizes[0]) == sizeof(ptrs) / sizeof(ptrs[0]), "scratch table");
-  int64_t total = 0;
-  for (int64_t s : sizes) total += (s + 63) / 64 * 64;
+  L->S2 = L->S3 = cfg->batch;  // per-sample conv2 / conv3 dW partials (bwd_bc_kernel)
+  // the scratch buffers in allocation order, sizes in floats (layout.hpp carve)
+  const Carve bufs[] = {
+      {&L->y1, Z * B * C1M * C1CO}, {&L->y2, Z * B * C2M * C2CO}, {&L->y3, Z * B * FLAT},
+      {&L->fc1p, Z * L->S_fc1 * B * HID}, {&L->h1, Z * B * HID}, {&L->q, Z * B * A},
+      {&L->dz1, B * HID}, {&L->dy3, B * FLAT}, {&L->dy2, B * C2M * C2CO}, {&L->dy1, B * C1M * C1CO},
+      {&L->p1, B * C1_BLOCKS * (C1KK + 1) * C1CO}, {&L->p2, B * (C2KK + 1) * C2CO}, {&L->p3, B * (C3KK + 1) * C3CO},
+      {&L->td, B}, {&L->loss, 1}, {&L->loss_part, B}, {&L->gq, B}, {&L->ga, B}, {&L->rec, 4 * B},
+      {&L->sync, SyncLayout{B}.ints()}, {&L->w3p, W3P_N}, {&L->w2p, W2P_N}, {&L->per_wb, 2 * B}};
+  const int64_t total = carve(bufs, nullptr);
   if (hipMalloc(&L->block, total * sizeof(float)) != hipSuccess) {
     delete L;
     return fail(DQZ_ERR_HIP, "hipMalloc of %lld bytes failed", (long long)(total * 4));
@@ -85,11 +80,7 @@ int dqz_learner_create(const dqz_learner_config* cfg, dqz_learner** out) {
     delete L;
     return fail(DQZ_ERR_HIP, "hipMemset of learner scratch failed");
   }
-  float* p = (float*)L->block;
-  for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) {
-    *ptrs[i] = p;
-    p += (sizes[i] + 63) / 64 * 64;
-  }
+  carve(bufs, (float*)L->block);
   *out = L;
   return DQZ_OK;
 }
@@ -133,44 +124,14 @@ int dqz_learner_destroy(dqz_learner* L) {
 // alternatives measured: DESIGN §4 "Tried in round 5"
 static int forward_impl(dqz_learner* L, const NetZ& nz, int Z, int B, const Conv1Src& src, hipStream_t st,
                         PhaseEvents pe) {
-  Conv1FwdArgs c1{};
-  c1.src = src;
-  c1.nz = nz;
-  c1.w_off = L->off[0];
-  c1.b_off = L->off[1];
-  c1.B = B;
-  c1.Z = Z;
-  c1.linear = 0;
-  c1.out = L->y1;
-
-  LayerFwdArgs c2{};
-  c2.in = L->y1;
-  c2.nz = nz;
-  c2.w_off = L->off[2];
-  c2.b_off = L->off[3];
-  c2.B = B;
-  c2.Z = Z;
-  c2.linear = 0;
-  c2.out = L->y2;
-
-  LayerFwdArgs c3 = c2;
-  c3.in = L->y2;
-  c3.w_off = L->off[4];
-  c3.b_off = L->off[5];
-  c3.out = L->y3;
-  // y1 / y2 hand-offs: 4 producer and 4 consumer blocks per sample.  The
-  // word layout follows the learner's configured batch, not this call's n
-  // (the actor's forward has n = 1): Z * n <= 3 * cfg.batch samples, and
-  // every launch shares the one error word dqz_learner_sync_status reads.
-  const int Bc = L->cfg.batch;
-  int* hw = L->sync + 2 * Bc * Handoff::kStride;
-  int* err = L->sync + 16 * Bc * Handoff::kStride;
+  FwdArgs a = make_fwd_args(L, nz, Z, B, src);
+  Conv1FwdArgs& c1 = a.c1;
+  LayerFwdArgs &c2 = a.c2, &c3 = a.c3;
+  // y1 / y2 hand-offs: 4 producer and `jobs` consumer blocks per sample
   const int jobs = fwd_conv_jobs(Z * B);
   c2.jobs = c3.jobs = jobs;
-  c1.pub = Handoff{hw, hw + 3 * Bc * Handoff::kStride, err, 4, jobs};
-  c2.wait = c1.pub;
-  c2.pub = Handoff{hw + 6 * Bc * Handoff::kStride, hw + 9 * Bc * Handoff::kStride, err, jobs, jobs};
-  c3.wait = c2.pub;
+  c1.pub = c2.wait = handoff(L, sync_of(L).fwd_y1(jobs));
+  c2.pub = c3.wait = handoff(L, sync_of(L).fwd_y2(jobs));
   const dim3 grid(xcd_grid(4, Z * B).x + 2 * xcd_grid(jobs, Z * B).x);
   DQZ_PHASE(0, switch (src.fused) {
     case 1: hipLaunchKernelGGL(fwd_conv_kernel<1>, grid, dim3(256), kConv1FwdSmem, st, c1, c2, c3); break;
@@ -181,13 +142,7 @@ static int forward_impl(dqz_learner* L, const NetZ& nz, int Z, int B, const Conv
   } DQZ_HIP(hipGetLastError()));
   if (pe.on()) pe.ms[1] = pe.ms[2] = 0.f;
 
-  Fc1FwdArgs f1{};
-  f1.in = L->y3;
-  f1.nz = nz;
-  f1.w_off = L->off[6];
-  f1.B = B;
-  f1.MG = (B + 31) / 32;
-  f1.part = L->fc1p;
+  const Fc1FwdArgs& f1 = a.f1;
   DQZ_PHASE(3, if (B <= FC1_GEMV_MAXB)
                  hipLaunchKernelGGL(fc1_gemv_kernel, dim3(fc1_fwd_blocks(Z, 1)), dim3(256), 0, st, f1);
                else
@@ -215,95 +170,99 @@ static HeadArgs make_head(dqz_learner* L, const NetZ& nz, int Z, int B) {
   return h;
 }
 
-// One learner step.  gout == null: centered RMSProp on P->online/mu/nu.
-// gout != null: gradient-output mode — the full gradient is written to gout
-// (dqz parameter layout) and P->online/mu/nu are left untouched.
-// meta_p != null: per-sample cotangents p_b * (-clip(td_b)) (MGSC meta mode).
-int dqz::step_impl(dqz_learner* L, const dqz_params* P, const dqz_store* S, const int32_t* slots,
-                   const float* is_weights, void* stream, PhaseEvents pe, float* gout, const float* meta_p,
-                   const UniformDraw* draw, int unit, int gacc, const PerWbArgs* wb, const SoftmaxDraw* sm,
-                   const PerSampleArgs* pd, const Rms* meta_epi, const HeadArgs* meta_sm, uint8_t* xout,
-                   const SoftmaxDrawExact* smx) {
-  if (!L || !P || !P->online || !P->target || !slots) return fail(DQZ_ERR_INVALID, "null argument");
-  if (!gout && !meta_epi && (!P->mu || !P->nu)) return fail(DQZ_ERR_INVALID, "null optimizer state");
-  if (meta_epi && meta_epi->meta == 1 && (!P->mu || !P->nu)) return fail(DQZ_ERR_INVALID, "null optimizer state");
-  if (int rc = check_store(S)) return rc;
-  if (L->cfg.algo == DQZ_ALGO_PER && !is_weights && !pd) return fail(DQZ_ERR_INVALID, "PER step needs is_weights");
-  hipStream_t st = (hipStream_t)stream;
-  const int B = L->cfg.batch, Z = L->Z, A = L->cfg.num_actions;
-  NetZ nz{};
-  nz.p[0] = P->online;
-  nz.p[1] = P->target;
-  nz.p[2] = P->online;
-  nz.which[0] = 0;
-  nz.which[1] = 1;
-  nz.which[2] = 1;
-  Conv1Src src{S->frames, S->fidx, slots, nullptr, 0, UniformDraw{}};
-  src.action = S->action;
-  src.reward = S->reward;
-  src.discount = S->discount;
-  src.rec = reinterpret_cast<float4*>(L->rec);
-  src.xout = xout;
-  if (draw || sm || pd || smx) {  // conv1 draws the batch itself; later kernels read the published slots
-    Conv1Src fsrc = src;
-    if (draw) {
-      fsrc.fused = 1;
-      fsrc.draw = *draw;
-    } else if (pd) {
-      fsrc.fused = 3;
-      fsrc.per = *pd;
-      fsrc.per.out_wb = L->per_wb;
-    } else if (smx) {
-      fsrc.fused = 4;
-      fsrc.smx = *smx;
-    } else {
-      fsrc.fused = 2;
-      fsrc.sm = *sm;
-    }
-    if (int rc = forward_impl(L, nz, Z, B, fsrc, st, pe)) return rc;
-  } else {
-    if (int rc = forward_impl(L, nz, Z, B, src, st, pe)) return rc;
+// The one place that decodes a request's batch source: the slots every kernel after conv1 reads and, for an
+// in-launch draw, Conv1Src::fused, the draw in fsrc's union (when fsrc is given) and the counter the head advances.
+struct Batch {
+  int fused;
+  const int32_t* slots;
+  uint64_t* advance;
+};
+static Batch decode_batch(const StepRequest& r, Conv1Src* fsrc) {
+  if (r.draw) {
+    if (fsrc) fsrc->draw = *r.draw;
+    return {1, r.draw->slots_out, r.draw->counter};
   }
+  if (r.sm) {
+    if (fsrc) fsrc->sm = *r.sm;
+    return {2, r.sm->slots_out, r.sm->counter};
+  }
+  if (r.pd) {
+    if (fsrc) fsrc->per = *r.pd;
+    return {3, r.pd->out_slots, r.pd->inj_u ? nullptr : r.pd->counter};  // injected uniforms: no counter is read
+  }
+  if (r.smx) {
+    if (fsrc) fsrc->smx = *r.smx;
+    return {4, r.smx->slots_out, r.smx->counter};
+  }
+  return {0, r.slots, nullptr};
+}
+
+int dqz::check_step(const dqz_learner* L, const dqz_params* P, const dqz_store* S, const StepRequest& r) {
+  if (!L || !P || !P->online || !P->target || !decode_batch(r, nullptr).slots)
+    return fail(DQZ_ERR_INVALID, "null argument");
+  if (!r.gout && !r.meta_epi && (!P->mu || !P->nu)) return fail(DQZ_ERR_INVALID, "null optimizer state");
+  if (r.meta_epi && r.meta_epi->meta == 1 && (!P->mu || !P->nu)) return fail(DQZ_ERR_INVALID, "null optimizer state");
+  if (int rc = check_store(S)) return rc;
+  if (L->cfg.algo == DQZ_ALGO_PER && !r.is_weights && !r.pd) return fail(DQZ_ERR_INVALID, "PER step needs is_weights");
+  if (!!r.draw + !!r.sm + !!r.smx + !!r.pd > 1) return fail(DQZ_ERR_INVALID, "a step takes at most one batch draw");
+  return DQZ_OK;
+}
+
+// One learner step as the request describes it (learner_impl.hpp StepRequest), already checked.
+int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, const StepRequest& r, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const PhaseEvents pe = r.pe;
+  const PerSampleArgs* const pd = r.pd;
+  const int B = L->cfg.batch, Z = L->Z, A = L->cfg.num_actions;
+  const NetZ nz{{P->online, P->target, P->online}, {0, 1, 1}};  // online(s_tm1), target(s_t), online(s_t)
+  Conv1Src fsrc{S->frames, S->fidx, nullptr, nullptr, 0, UniformDraw{}};  // the forward's, draw included
+  fsrc.action = S->action;
+  fsrc.reward = S->reward;
+  fsrc.discount = S->discount;
+  fsrc.rec = reinterpret_cast<float4*>(L->rec);
+  fsrc.xout = r.xout;
+  Conv1Src src = fsrc;  // conv1 dW's: the published slots, no draw
+  const Batch batch = decode_batch(r, &fsrc);
+  fsrc.fused = batch.fused;
+  fsrc.slots = src.slots = batch.slots;
+  if (pd) fsrc.per.out_wb = L->per_wb;
+  if (int rc = forward_impl(L, nz, Z, B, fsrc, st, pe)) return rc;
 
   // an MGSC meta stage applied in the gradient epilogues (Rms), or plain
   // RMSProp / gradient output: every field set (value-initialised first)
   Rms rms{};
-  if (meta_epi) rms = *meta_epi;
+  if (r.meta_epi) rms = *r.meta_epi;
   rms.lr = L->cfg.learning_rate;
   rms.decay = L->cfg.decay;
   rms.c1 = (float)(1.0 - (double)L->cfg.decay);
   rms.eps = L->cfg.eps;
-  rms.gout = gout;
-  rms.gacc = gacc;
+  rms.gout = r.gout;
+  rms.gacc = r.gacc;
   rms.sq_off = 0;
 
   HeadArgs h = make_head(L, nz, Z, B);
   h.fwd_only = 0;
-  h.slots = slots;
+  h.slots = batch.slots;
   h.action = S->action;
   h.reward = S->reward;
   h.discount = S->discount;
-  h.weights = L->cfg.algo == DQZ_ALGO_PER && !pd ? is_weights : nullptr;
+  h.weights = L->cfg.algo == DQZ_ALGO_PER && !pd ? r.is_weights : nullptr;
   if (pd) {
     h.per_wb = L->per_wb;
     h.per_normalize = pd->normalize;
     h.per_w_out = pd->out_weights;
   }
-  h.meta_p = meta_p;
-  if (meta_sm) {  // the meta batch's softmax formed by the head (one meta chunk)
-    h.meta_logits = meta_sm->meta_logits;
-    h.meta_pos = meta_sm->meta_pos;
-    h.meta_M = meta_sm->meta_M;
-    h.meta_x_out = meta_sm->meta_x_out;
-    h.meta_p_out = meta_sm->meta_p_out;
+  h.meta_p = r.meta_p;
+  if (const MetaSoftmax* m = r.meta_sm) {
+    h.meta_logits = m->logits;
+    h.meta_pos = m->pos;
+    h.meta_M = m->M;
+    h.meta_x_out = m->x_out;
+    h.meta_p_out = m->p_out;
   }
   h.rec = reinterpret_cast<const float4*>(L->rec);
-  h.advance = draw  ? draw->counter
-              : sm  ? sm->counter
-              : smx ? smx->counter
-              : pd  ? (pd->inj_u ? nullptr : pd->counter)
-                    : nullptr;
-  h.unit = unit;
+  h.advance = batch.advance;
+  h.unit = r.unit;
   h.bound = L->cfg.grad_error_bound;
   h.td = L->td;
   h.loss_part = L->loss_part;
@@ -345,10 +304,7 @@ int dqz::step_impl(dqz_learner* L, const dqz_params* P, const dqz_store* S, cons
   c3b.dy2 = L->dy2;
   c3b.part = L->p3;
   c3b.B = B;
-  // hand-off words (units of Handoff::kStride ints): dy2 cnt [0, B), ack [B, 2B);
-  // forward y1 / y2 [2B, 14B); dy1 cnt [14B, 15B), ack [15B, 16B); err at 16B
-  int* const herr = L->sync + 16 * B * Handoff::kStride;
-  c3b.sync = Handoff{L->sync, L->sync + B * Handoff::kStride, herr, 8, 16, L->spin_max};
+  c3b.sync = handoff(L, sync_of(L).dy2());
   Conv2BwdArgs c2b{};
   c2b.dy2 = L->dy2;
   c2b.y1 = L->y1;
@@ -366,13 +322,13 @@ int dqz::step_impl(dqz_learner* L, const dqz_params* P, const dqz_store* S, cons
   c1dw.B = B;
   c1dw.dy1 = L->dy1;
   c1dw.part = L->p1;
-  c1dw.sync1 = Handoff{L->sync + 14 * B * Handoff::kStride, L->sync + 15 * B * Handoff::kStride, herr, 8, 8,
-                       L->spin_max};
+  c1dw.sync1 = handoff(L, sync_of(L).dy1());
   c2b.sync1 = c1dw.sync1;
   const int B8 = (B + 7) / 8 * 8;
   PerWbArgs wbk{};
+  const bool wb = r.wb != nullptr;
   if (wb) {
-    wbk = *wb;
+    wbk = *r.wb;
     wbk.td = L->td;
     wbk.n = B;
   }
@@ -402,7 +358,7 @@ int dqz::step_impl(dqz_learner* L, const dqz_params* P, const dqz_store* S, cons
   u.ga = L->ga;
   u.loss_part = L->loss_part;
   u.loss = L->loss;
-  u.status = herr;
+  u.status = L->sync + sync_of(L).err();
   u.A = A;
   u.B = B;
   u.nb2 = L->shared_bias ? 1 : A;
@@ -418,7 +374,7 @@ extern "C" {
 
 int dqz_learner_step(dqz_learner* L, const dqz_params* P, const dqz_store* S, const int32_t* slots,
                      const float* is_weights, void* stream) {
-  return step_impl(L, P, S, slots, is_weights, stream, kNoProfile);
+  return step_impl(L, P, S, {.slots = slots, .is_weights = is_weights}, stream);
 }
 
 int dqz_learner_step_per(dqz_learner* L, const dqz_params* P, const dqz_store* S, const int32_t* slots,
@@ -427,28 +383,24 @@ int dqz_learner_step_per(dqz_learner* L, const dqz_params* P, const dqz_store* S
   if (!L || !tree || !indices || !max_seen_dev) return fail(DQZ_ERR_INVALID, "null argument");
   if (L->cfg.batch > 64) return fail(DQZ_ERR_INVALID, "the fused write-back takes batch <= 64 (use dqz_per_write_back)");
   if (cap < 1 || (cap & (cap - 1))) return fail(DQZ_ERR_INVALID, "cap must be a power of two");
-  int levels = 0;
-  while (((int64_t)1 << levels) < cap) ++levels;
-  if (levels > PWB_LEVELS) return fail(DQZ_ERR_INVALID, "cap must be <= 2^%d for the fused write-back", PWB_LEVELS);
-  PerWbArgs wb{tree, cap, levels, indices, nullptr, alpha, 0, max_seen_dev};
-  return step_impl(L, P, S, slots, is_weights, stream, kNoProfile, nullptr, nullptr, nullptr, 0, 0, &wb);
+  PerWbArgs wb;
+  if (!per_wb_args(L, tree, cap, indices, alpha, max_seen_dev, &wb))
+    return fail(DQZ_ERR_INVALID, "cap must be <= 2^%d for the fused write-back", PWB_LEVELS);
+  return step_impl(L, P, S, {.slots = slots, .is_weights = is_weights, .wb = &wb}, stream);
 }
 
 int dqz_learner_step_uniform(dqz_learner* L, const dqz_params* P, const dqz_store* S, int64_t base, int64_t size,
                              int64_t capacity, uint64_t seed, uint64_t* counter_dev, int32_t* slots_out,
                              void* stream) {
-  if (!counter_dev || !slots_out) return fail(DQZ_ERR_INVALID, "null argument");
-  if (size < 1) return fail(DQZ_ERR_INVALID, "cannot sample from an empty replay (size=%lld)", (long long)size);
-  if (capacity < size || base < 0) return fail(DQZ_ERR_INVALID, "bad replay geometry");
-  if (L && L->cfg.algo == DQZ_ALGO_PER) return fail(DQZ_ERR_INVALID, "PER samples by priority, not uniformly");
-  const UniformDraw d{base % capacity, size, capacity, seed, counter_dev, slots_out};
-  return step_impl(L, P, S, slots_out, nullptr, stream, kNoProfile, nullptr, nullptr, &d);
+  UniformDraw d;
+  if (int rc = uniform_draw_args(L, base, size, capacity, seed, counter_dev, slots_out, &d)) return rc;
+  return step_impl(L, P, S, {.draw = &d}, stream);
 }
 
 int dqz_learner_grad(dqz_learner* L, const dqz_params* P, const dqz_store* S, const int32_t* slots,
                      const float* is_weights, float* grad_out, void* stream) {
   if (!grad_out) return fail(DQZ_ERR_INVALID, "null grad_out");
-  return step_impl(L, P, S, slots, is_weights, stream, kNoProfile, grad_out);
+  return step_impl(L, P, S, {.slots = slots, .is_weights = is_weights, .gout = grad_out}, stream);
 }
 
 int dqz_learner_profile(dqz_learner* L, const dqz_params* P, const dqz_store* S, const int32_t* slots,
@@ -458,7 +410,7 @@ int dqz_learner_profile(dqz_learner* L, const dqz_params* P, const dqz_store* S,
   PhaseEvents pe{nullptr, nullptr, iters, phase_ms};
   DQZ_HIP(hipEventCreate(&pe.e0));
   DQZ_HIP(hipEventCreate(&pe.e1));
-  const int rc = step_impl(L, P, S, slots, is_weights, stream, pe);
+  const int rc = step_impl(L, P, S, {.slots = slots, .is_weights = is_weights, .pe = pe}, stream);
   (void)hipEventDestroy(pe.e0);
   (void)hipEventDestroy(pe.e1);
   return rc;
@@ -467,14 +419,14 @@ int dqz_learner_profile(dqz_learner* L, const dqz_params* P, const dqz_store* S,
 int dqz_learner_sync_status(dqz_learner* L, int* status) {
   if (!L || !status) return fail(DQZ_ERR_INVALID, "null argument");
   DQZ_HIP(hipDeviceSynchronize());
-  DQZ_HIP(hipMemcpy(status, L->sync + 16 * L->cfg.batch * Handoff::kStride, sizeof(int), hipMemcpyDeviceToHost));
+  DQZ_HIP(hipMemcpy(status, L->sync + sync_of(L).err(), sizeof(int), hipMemcpyDeviceToHost));
   if (*status != 0) {
     // A wait gave up: its consumers ran on partial payloads and producers may
     // have arrived after the last consumer reset the words, which would let
     // later launches pass their waits early.  Clear every hand-off word (and
     // the error word) so the next step starts clean; the caller must treat
     // the steps since the previous check as invalid.
-    DQZ_HIP(hipMemset(L->sync, 0, sizeof(int) * ((16 * L->cfg.batch + 3) * Handoff::kStride + 64)));
+    DQZ_HIP(hipMemset(L->sync, 0, sizeof(int) * sync_of(L).ints()));
     DQZ_HIP(hipDeviceSynchronize());
   }
   return DQZ_OK;
@@ -486,9 +438,9 @@ int dqz_learner_debug_stall(dqz_learner* L, int sample, unsigned spin_max) {
   L->spin_max = spin_max ? spin_max : 1u << 24;
   if (sample >= 0) {  // sample's dy2 arrival counter far below its 8 arrivals: its waits run out
     const int32_t poison = -(1 << 30);
+    const SyncLayout at = sync_of(L);
     DQZ_HIP(hipDeviceSynchronize());
-    DQZ_HIP(hipMemcpy(L->sync + (int64_t)sample * Handoff::kStride, &poison, sizeof(poison),
-                      hipMemcpyHostToDevice));
+    DQZ_HIP(hipMemcpy(L->sync + at.dy2().cnt + at.word(sample), &poison, sizeof(poison), hipMemcpyHostToDevice));
   }
   return DQZ_OK;
 }
@@ -505,10 +457,8 @@ int dqz_learner_outputs(dqz_learner* L, float* q_tm1, float* td, float* loss, vo
 
 static int forward_q(dqz_learner* L, const float* params, const Conv1Src& src, int which, int n, float* q_out,
                      hipStream_t st) {
-  NetZ nz{};
-  nz.p[0] = nz.p[1] = nz.p[2] = params;
-  nz.which[0] = nz.which[1] = nz.which[2] = which;
-  if (int rc = forward_impl(L, nz, 1, n, src, st, kNoProfile)) return rc;
+  const NetZ nz{{params, params, params}, {which, which, which}};
+  if (int rc = forward_impl(L, nz, 1, n, src, st, PhaseEvents{})) return rc;
   HeadArgs h = make_head(L, nz, 1, n);
   h.fwd_only = 1;
   h.q = q_out;
@@ -545,11 +495,9 @@ int dqz_act(dqz_learner* L, const float* params, const uint8_t* states, int n, d
   if (int rc = device_view(out, &dout, "out")) return rc;
   if (reinterpret_cast<uintptr_t>(dstates) % 16) return fail(DQZ_ERR_INVALID, "states must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  NetZ nz{};
-  nz.p[0] = nz.p[1] = nz.p[2] = params;
-  nz.which[0] = nz.which[1] = nz.which[2] = 0;
+  const NetZ nz{{params, params, params}, {0, 0, 0}};
   Conv1Src src{nullptr, nullptr, nullptr, static_cast<const uint8_t*>(dstates), 0, UniformDraw{}};
-  if (int rc = forward_impl(L, nz, 1, n, src, st, kNoProfile)) return rc;
+  if (int rc = forward_impl(L, nz, 1, n, src, st, PhaseEvents{})) return rc;
   HeadArgs h = make_head(L, nz, 1, n);
   h.fwd_only = 1;
   h.q = L->q;
