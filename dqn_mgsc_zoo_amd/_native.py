@@ -234,6 +234,39 @@ SIGNATURES = {
         _int,
         [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore),
          ctypes.POINTER(DqzPerDraw), _vp, _vp, _vp]),
+    'dqz_c51_param_layout': (
+        _int,
+        [_int, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+         ctypes.POINTER(_i64)],
+    ),
+    'dqz_c51_optimizer_create': (
+        _int, [ctypes.POINTER(DqzOptimizerConfig), _int, ctypes.POINTER(_vp)]),
+    'dqz_c51_create': (
+        _int, [ctypes.POINTER(DqzLearnerConfig), _int, _vp,
+               ctypes.POINTER(_vp)]),
+    'dqz_c51_destroy': (_int, [_vp]),
+    'dqz_c51_learner': (_int, [_vp, ctypes.POINTER(_vp)]),
+    'dqz_c51_step': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
+         _vp, _vp]),
+    'dqz_c51_grad': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
+         _vp]),
+    'dqz_c51_outputs': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dqz_c51_debug': (_int, [_vp, _vp, _vp, _vp]),
+    'dqz_c51_profile': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
+         _int, ctypes.POINTER(ctypes.c_float), _vp]),
+    'dqz_c51_forward': (_int, [_vp, _vp, _vp, _int, _vp, _vp]),
+    'dqz_c51_forward_slots': (
+        _int, [_vp, _vp, ctypes.POINTER(DqzStore), _vp, _int, _int, _vp, _vp]),
+    'dqz_c51_act': (
+        _int, [_vp, _vp, _vp, _int, ctypes.c_double, ctypes.c_uint64,
+               ctypes.c_uint64, _vp, _vp]),
+    'dqz_c51_debug_check': (_int, [_int, ctypes.c_uint]),
     'dqz_learner_grad': (
         _int,
         [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
@@ -390,6 +423,22 @@ def param_layout(num_actions, shared_bias):
       int(num_actions), int(bool(shared_bias)), offs, sizes,
       ctypes.byref(total)))
   return list(offs), list(sizes), int(total.value)
+
+
+def c51_param_layout(num_actions, num_atoms):
+  """(offsets, sizes, total) of the categorical network's flat buffer."""
+  offs = (_i64 * NUM_LEAVES)()
+  sizes = (_i64 * NUM_LEAVES)()
+  total = _i64()
+  check(lib().dqz_c51_param_layout(
+      int(num_actions), int(num_atoms), offs, sizes, ctypes.byref(total)))
+  return list(offs), list(sizes), int(total.value)
+
+
+# dqz_c51_debug_check's request bits (DQZ_C51_REQ_*)
+C51_REQ = dict(weights=1, per_draw=2, uniform_draw=4, logit_draw=8,
+               exact_draw=16, meta_p=32, meta_epi=64, meta_softmax=128,
+               unit=256, write_back=512, fused_rmsprop=1024)
 
 
 def ptr(t):

@@ -59,10 +59,8 @@ class DeviceDqnAgent(parts.Agent):
     self._act_seed = seed
     self._act_count = 0
     self._network = network
-    self._learner = learner_lib.Learner(network, batch_size, algo=self._ALGO,
-                                        optimizer=optimizer,
-                                        grad_error_bound=grad_error_bound,
-                                        device=device)
+    self._learner = self._new_learner(network, batch_size, optimizer,
+                                      grad_error_bound, device)
     self._learner.set_params(network.init(seed))
     self._action = None
     self._frame_t = -1
@@ -70,6 +68,13 @@ class DeviceDqnAgent(parts.Agent):
     self._learn_steps = 0
     self._last_health_check = 0  # learn steps done at the previous check
     self._nonfinite_loss_checks = 0
+
+  def _new_learner(self, network, batch_size, optimizer, grad_error_bound,
+                   device) -> learner_lib.Learner:
+    """The device learner of this agent (the categorical agent has its own)."""
+    return learner_lib.Learner(network, batch_size, algo=self._ALGO,
+                               optimizer=optimizer,
+                               grad_error_bound=grad_error_bound, device=device)
 
   # -- reference surface ----------------------------------------------------
 

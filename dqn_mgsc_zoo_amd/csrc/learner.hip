@@ -3,7 +3,8 @@
 // the replay-side device code (frame store puts and gathers, the uniform,
 // learned-logit and prioritized samplers, sum trees), the MGSC meta-update
 // and its HVP, Atari preprocessing, the optimizers applied to a finished
-// gradient (Adam, plain RMSProp, global-norm clipping), and the C-ABI entries
+// gradient (Adam, plain RMSProp, global-norm clipping), the categorical (C51)
+// head the learner step launches in place of its own, and the C-ABI entries
 // that drive them.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,7 @@
 #include "preprocess.hpp"
 #include "census.hpp"
 #include "optim.hpp"
+#include "c51.hpp"
 
 using namespace dqz;
 
@@ -654,10 +656,12 @@ struct dqz_optimizer {
   float* grad;        // [total] the steps' gradient; padding zero since creation
   double* part;       // [nparts] sums of squares of the last gradient normed
   const float* last;  // the most recent apply's gradient (dqz_optimizer_outputs without clipping)
+  int num_atoms;      // 0: dqz_param_layout; N: the categorical head's layout (dqz_c51_param_layout)
   void* block;
 };
 
-int dqz_optimizer_create(const dqz_optimizer_config* cfg, dqz_optimizer** out) {
+// num_atoms = 0: the scalar head's layout; N: the categorical head's (fc2 leaves A * N wide, no shared bias)
+static int optimizer_create(const dqz_optimizer_config* cfg, int num_atoms, dqz_optimizer** out) {
   if (!cfg || !out) return fail(DQZ_ERR_INVALID, "null argument");
   if (cfg->kind != DQZ_OPT_ADAM && cfg->kind != DQZ_OPT_RMSPROP)
     return fail(DQZ_ERR_INVALID, "optimizer kind must be DQZ_OPT_ADAM or DQZ_OPT_RMSPROP");
@@ -669,8 +673,12 @@ int dqz_optimizer_create(const dqz_optimizer_config* cfg, dqz_optimizer** out) {
     return fail(DQZ_ERR_INVALID, "decay must be in [0, 1]");
   dqz_optimizer* o = new dqz_optimizer();
   o->cfg = *cfg;
+  o->num_atoms = num_atoms;
   int64_t off[10], sz[10];
-  param_layout(cfg->num_actions, cfg->shared_bias, off, sz, &o->total);
+  if (num_atoms)
+    c51_param_layout(cfg->num_actions, num_atoms, off, sz, &o->total);
+  else
+    param_layout(cfg->num_actions, cfg->shared_bias, off, sz, &o->total);
   for (int i = 0; i < 10; ++i) {
     o->lv.off4[i] = off[i] / 4;
     o->lv.end[i] = off[i] + sz[i];
@@ -690,6 +698,10 @@ int dqz_optimizer_create(const dqz_optimizer_config* cfg, dqz_optimizer** out) {
   o->last = nullptr;
   *out = o;
   return DQZ_OK;
+}
+
+int dqz_optimizer_create(const dqz_optimizer_config* cfg, dqz_optimizer** out) {
+  return optimizer_create(cfg, 0, out);
 }
 
 int dqz_optimizer_destroy(dqz_optimizer* o) {
@@ -765,7 +777,7 @@ static int check_step_opt(const dqz_learner* L, const dqz_params* P, const dqz_o
   if ((reinterpret_cast<uintptr_t>(P->online) | reinterpret_cast<uintptr_t>(P->nu) |
        reinterpret_cast<uintptr_t>(P->mu)) % 16)
     return fail(DQZ_ERR_INVALID, "parameters and moments must be 16-byte aligned");
-  if (o->cfg.num_actions != L->cfg.num_actions || (o->cfg.shared_bias != 0) != (L->shared_bias != 0))
+  if (o->cfg.num_actions != L->cfg.num_actions || (o->cfg.shared_bias != 0) != (L->shared_bias != 0) || o->num_atoms)
     return fail(DQZ_ERR_INVALID, "the optimizer was created for another parameter layout");
   return DQZ_OK;
 }
@@ -835,6 +847,342 @@ int dqz_learner_debug_activations(dqz_learner* L, int z, float* y1, float* y2, f
     if (r.dst)
       DQZ_HIP(hipMemcpyAsync(r.dst, r.src + r.zc * B * r.n, sizeof(float) * B * r.n, hipMemcpyDeviceToDevice, st));
   return DQZ_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// the categorical (C51) agent (c51.hpp)
+
+static_assert(C51_MAX_ATOMS == C51_MAXN && C51_MAX_OUT == C51_MAXOUT, "learner_impl.hpp restates c51.hpp's limits");
+
+// A dqz_learner on the categorical layout plus the head's own buffers.
+struct dqz_c51 {
+  dqz_learner* L;
+  int A, N;
+  C51Head head;  // support and outputs, carved from block
+  void* block;
+};
+
+static int c51_check_shape(int A, int N) {
+  if (A < 1 || A > MAXA) return fail(DQZ_ERR_INVALID, "num_actions must be in [1, %d]", MAXA);
+  if (N < 2 || N > C51_MAXN) return fail(DQZ_ERR_INVALID, "num_atoms must be in [2, %d]", C51_MAXN);
+  if (A * N > C51_MAXOUT) return fail(DQZ_ERR_INVALID, "num_actions * num_atoms must be <= %d", C51_MAXOUT);
+  return DQZ_OK;
+}
+
+static int c51_logits(dqz_learner* L, const NetZ& nz, int Z, int B, int AN, float* logits, hipStream_t st) {
+  if (L->S_fc1 > FC1_S) return fail(DQZ_ERR_INVALID, "the categorical head takes at most %d fc1 partials", FC1_S);
+  for (int z = 0; z < Z; ++z)  // the kernel reads fc1/b as float4
+    if (reinterpret_cast<uintptr_t>(nz.p[z]) % 16) return fail(DQZ_ERR_INVALID, "parameters must be 16-byte aligned");
+  C51LogitsArgs a{};
+  a.fc1p = L->fc1p;
+  a.S = L->S_fc1;
+  a.h1 = L->h1;
+  a.nz = nz;
+  a.b1_off = L->off[7];
+  a.w2_off = L->off[8];
+  a.b2_off = L->off[9];
+  a.Z = Z;
+  a.B = B;
+  a.AN = AN;
+  a.logits = logits;
+  const dim3 grid((AN + C51_COLS - 1) / C51_COLS, Z * ((B + C51_ROWS - 1) / C51_ROWS));
+  hipLaunchKernelGGL(c51_logits_kernel, grid, dim3(256), 0, st, a);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+int dqz::c51_launch(C51Launch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const C51Head& c = *r.c51;
+  const int B = L->cfg.batch, A = L->cfg.num_actions, N = c.N;
+  if (which == C51_LOGITS) {
+    const NetZ nz{{P->online, P->target, P->online}, {0, 1, 1}};
+    return c51_logits(L, nz, 2, B, A * N, c.logits, st);
+  }
+  if (which == C51_HEAD) {
+    C51HeadArgs h{};
+    h.logits = c.logits;
+    h.h1 = L->h1;
+    h.w2 = P->online + L->off[8];
+    h.support = c.support;
+    h.Z = 2;
+    h.B = B;
+    h.A = A;
+    h.N = N;
+    h.rec = reinterpret_cast<const float4*>(L->rec);
+    h.qv = c.qv;
+    h.la = c.la;
+    h.dl = c.dl;
+    h.astar = c.astar;
+    h.loss_part = L->loss_part;
+    h.gq = L->gq;
+    h.ga = L->ga;
+    h.dz1 = L->dz1;
+    hipLaunchKernelGGL(c51_head_kernel, dim3(B), dim3(HID), 0, st, h);
+    DQZ_HIP(hipGetLastError());
+    return DQZ_OK;
+  }
+  C51GradArgs g{};
+  g.h1 = L->h1;
+  g.dl = c.dl;
+  g.ga = L->ga;
+  g.B = B;
+  g.A = A;
+  g.N = N;
+  g.gw = r.gout + L->off[8];
+  g.gb = r.gout + L->off[9];
+  g.acc = r.gacc;
+  const int64_t elems = (int64_t)(HID + 1) * A * N;
+  hipLaunchKernelGGL(c51_fc2_grad_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, g);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+// q_values of n states through one copy: the torso, the logits, the head in forward mode (actor: with a draw)
+static int c51_forward_q(dqz_c51* C, const float* params, const Conv1Src& src, int which, int n, float* q_out,
+                         dqz_action* act_out, double eps, uint64_t seed, uint64_t counter, hipStream_t st) {
+  dqz_learner* L = C->L;
+  if (int rc = forward_torso(L, params, src, which, n, st)) return rc;
+  const NetZ nz{{params, params, params}, {which, which, which}};
+  if (int rc = c51_logits(L, nz, 1, n, C->A * C->N, C->head.logits, st)) return rc;
+  C51HeadArgs h{};
+  h.logits = C->head.logits;
+  h.support = C->head.support;
+  h.Z = 1;
+  h.B = n;
+  h.A = C->A;
+  h.N = C->N;
+  h.fwd_only = 1;
+  h.qv = q_out;
+  h.act_out = act_out;
+  h.eps = eps;
+  h.act_seed = seed;
+  h.act_ctr = counter;
+  hipLaunchKernelGGL(c51_head_kernel, dim3(n), dim3(HID), 0, st, h);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+static int c51_check_step(const dqz_c51* C, const dqz_params* P, const dqz_optimizer* o, const int32_t* count) {
+  if (!C || !P || !o) return fail(DQZ_ERR_INVALID, "null argument");
+  if (!P->online || !P->nu) return fail(DQZ_ERR_INVALID, "null optimizer state");
+  if (o->cfg.kind == DQZ_OPT_ADAM && (!P->mu || !count)) return fail(DQZ_ERR_INVALID, "Adam needs mu and count");
+  if ((reinterpret_cast<uintptr_t>(P->online) | reinterpret_cast<uintptr_t>(P->nu) |
+       reinterpret_cast<uintptr_t>(P->mu)) % 16)
+    return fail(DQZ_ERR_INVALID, "parameters and moments must be 16-byte aligned");
+  if (o->cfg.num_actions != C->A || o->num_atoms != C->N)
+    return fail(DQZ_ERR_INVALID, "the optimizer was created for another parameter layout");
+  return DQZ_OK;
+}
+
+extern "C" {
+
+int dqz_c51_param_layout(int num_actions, int num_atoms, int64_t offsets[10], int64_t sizes[10], int64_t* total) {
+  if (int rc = c51_check_shape(num_actions, num_atoms)) return rc;
+  if (!offsets || !sizes || !total) return fail(DQZ_ERR_INVALID, "null output pointer");
+  c51_param_layout(num_actions, num_atoms, offsets, sizes, total);
+  return DQZ_OK;
+}
+
+int dqz_c51_optimizer_create(const dqz_optimizer_config* cfg, int num_atoms, dqz_optimizer** out) {
+  if (!cfg || !out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (int rc = c51_check_shape(cfg->num_actions, num_atoms)) return rc;
+  if (cfg->shared_bias) return fail(DQZ_ERR_INVALID, "the categorical head has no shared bias");
+  return optimizer_create(cfg, num_atoms, out);
+}
+
+int dqz_c51_create(const dqz_learner_config* cfg, int num_atoms, const float* support, dqz_c51** out) {
+  if (!cfg || !support || !out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (int rc = c51_check_shape(cfg->num_actions, num_atoms)) return rc;
+  if (cfg->batch < 2 || cfg->batch > MAXB) return fail(DQZ_ERR_INVALID, "batch must be in [2, %d]", MAXB);
+  if (cfg->algo != DQZ_ALGO_DQN) return fail(DQZ_ERR_INVALID, "the categorical head runs on a DQN learner");
+  // the support, checked on the host (this call may synchronise; the step never does)
+  float z[C51_MAXN];
+  DQZ_HIP(hipMemcpy(z, support, sizeof(float) * num_atoms, hipMemcpyDefault));
+  for (int i = 0; i < num_atoms; ++i)
+    if (!std::isfinite(z[i]) || (i > 0 && !(z[i] > z[i - 1])))
+      return fail(DQZ_ERR_INVALID, "support must be finite and strictly increasing (atom %d)", i);
+  dqz_learner* L = nullptr;
+  if (int rc = dqz_learner_create(cfg, &L)) return rc;
+  const int A = cfg->num_actions, N = num_atoms;
+  c51_param_layout(A, N, L->off, L->sz, &L->total);  // leaves 0-7 unchanged; the scalar head's L->q stays unused
+  dqz_c51* C = new dqz_c51();
+  C->L = L;
+  C->A = A;
+  C->N = N;
+  const int64_t B = cfg->batch;
+  const int64_t n_sup = (N + 63) / 64 * 64, n_lg = 2 * B * A * N, n_la = B * N, n_qv = (2 * B * A + 63) / 64 * 64;
+  const int64_t floats = n_sup + n_lg + 2 * n_la + n_qv + B;
+  if (hipMalloc(&C->block, floats * sizeof(float)) != hipSuccess ||
+      hipMemset(C->block, 0, floats * sizeof(float)) != hipSuccess) {
+    if (C->block) (void)hipFree(C->block);
+    (void)dqz_learner_destroy(L);
+    delete C;
+    return fail(DQZ_ERR_HIP, "hipMalloc of %lld bytes of categorical-head scratch failed", (long long)(floats * 4));
+  }
+  float* p = (float*)C->block;
+  float* sup = p;
+  C->head.N = N;
+  C->head.support = sup;
+  C->head.logits = p + n_sup;
+  C->head.la = C->head.logits + n_lg;
+  C->head.dl = C->head.la + n_la;
+  C->head.qv = C->head.dl + n_la;
+  C->head.astar = reinterpret_cast<int32_t*>(C->head.qv + n_qv);
+  if (hipMemcpy(sup, z, sizeof(float) * N, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)dqz_c51_destroy(C);
+    return fail(DQZ_ERR_HIP, "copy of the support failed");
+  }
+  *out = C;
+  return DQZ_OK;
+}
+
+int dqz_c51_destroy(dqz_c51* C) {
+  if (!C) return DQZ_OK;
+  if (C->block) (void)hipFree(C->block);
+  (void)dqz_learner_destroy(C->L);
+  delete C;
+  return DQZ_OK;
+}
+
+int dqz_c51_learner(dqz_c51* C, dqz_learner** out) {
+  if (!C || !out) return fail(DQZ_ERR_INVALID, "null argument");
+  *out = C->L;
+  return DQZ_OK;
+}
+
+int dqz_c51_step(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, dqz_optimizer* o,
+                 int32_t* count, void* stream) {
+  if (int rc = c51_check_step(C, P, o, count)) return rc;
+  if (int rc = step_impl(C->L, P, S, {.slots = slots, .gout = o->grad, .c51 = &C->head}, stream)) return rc;
+  return dqz_optimizer_apply(o, P->online, o->grad, P->mu, P->nu, count, stream);
+}
+
+int dqz_c51_grad(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
+                 void* stream) {
+  if (!C) return fail(DQZ_ERR_INVALID, "null argument");
+  if (!grad_out) return fail(DQZ_ERR_INVALID, "null grad_out");
+  return step_impl(C->L, P, S, {.slots = slots, .gout = grad_out, .c51 = &C->head}, stream);
+}
+
+int dqz_c51_profile(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
+                    int iters, float* phase_ms, void* stream) {
+  if (!C) return fail(DQZ_ERR_INVALID, "null argument");
+  if (!grad_out) return fail(DQZ_ERR_INVALID, "null grad_out");
+  if (!phase_ms || iters < 1) return fail(DQZ_ERR_INVALID, "phase_ms must be non-null and iters >= 1");
+  for (int i = 0; i < DQZ_NUM_PHASES; ++i) phase_ms[i] = 0.f;
+  PhaseEvents pe{nullptr, nullptr, iters, phase_ms};
+  DQZ_HIP(hipEventCreate(&pe.e0));
+  DQZ_HIP(hipEventCreate(&pe.e1));
+  const int rc = step_impl(C->L, P, S, {.slots = slots, .gout = grad_out, .pe = pe, .c51 = &C->head}, stream);
+  (void)hipEventDestroy(pe.e0);
+  (void)hipEventDestroy(pe.e1);
+  return rc;
+}
+
+int dqz_c51_outputs(dqz_c51* C, float* logits_a, float* q_values, float* loss_b, float* loss, int32_t* a_star,
+                    void* stream) {
+  if (!C) return fail(DQZ_ERR_INVALID, "null argument");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t B = C->L->cfg.batch;
+  const struct {
+    void* dst;
+    const void* src;
+    int64_t n;
+  } rows[] = {{logits_a, C->head.la, B * C->N},  {q_values, C->head.qv, 2 * B * C->A}, {loss_b, C->L->loss_part, B},
+              {loss, C->L->loss, 1},             {a_star, C->head.astar, B}};
+  for (const auto& r : rows)
+    if (r.dst) DQZ_HIP(hipMemcpyAsync(r.dst, r.src, 4 * r.n, hipMemcpyDeviceToDevice, st));
+  return DQZ_OK;
+}
+
+int dqz_c51_debug(dqz_c51* C, float* logits, float* dlogits, void* stream) {
+  if (!C) return fail(DQZ_ERR_INVALID, "null argument");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t B = C->L->cfg.batch;
+  if (logits)
+    DQZ_HIP(hipMemcpyAsync(logits, C->head.logits, 4 * 2 * B * C->A * C->N, hipMemcpyDeviceToDevice, st));
+  if (dlogits) DQZ_HIP(hipMemcpyAsync(dlogits, C->head.dl, 4 * B * C->N, hipMemcpyDeviceToDevice, st));
+  return DQZ_OK;
+}
+
+int dqz_c51_forward(dqz_c51* C, const float* params, const uint8_t* states, int n, float* q_out, void* stream) {
+  if (!C || !params || !states || !q_out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (n < 1 || n > C->L->cfg.batch) return fail(DQZ_ERR_INVALID, "n must be in [1, %d]", C->L->cfg.batch);
+  if (reinterpret_cast<uintptr_t>(states) % 16) return fail(DQZ_ERR_INVALID, "states must be 16-byte aligned");
+  Conv1Src src{nullptr, nullptr, nullptr, states, 0, UniformDraw{}};
+  return c51_forward_q(C, params, src, 0, n, q_out, nullptr, 0.0, 0, 0, (hipStream_t)stream);
+}
+
+int dqz_c51_forward_slots(dqz_c51* C, const float* params, const dqz_store* S, const int32_t* slots, int n, int which,
+                          float* q_out, void* stream) {
+  if (!C || !params || !slots || !q_out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (int rc = check_store(S)) return rc;
+  if (n < 1 || n > C->L->cfg.batch) return fail(DQZ_ERR_INVALID, "n must be in [1, %d]", C->L->cfg.batch);
+  if (which != 0 && which != 1) return fail(DQZ_ERR_INVALID, "which must be 0 (s_tm1) or 1 (s_t)");
+  Conv1Src src{S->frames, S->fidx, slots, nullptr, 0, UniformDraw{}};
+  return c51_forward_q(C, params, src, which, n, q_out, nullptr, 0.0, 0, 0, (hipStream_t)stream);
+}
+
+int dqz_c51_act(dqz_c51* C, const float* params, const uint8_t* states, int n, double epsilon, uint64_t seed,
+                uint64_t counter, dqz_action* out, void* stream) {
+  if (!C || !params || !states || !out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (n < 1 || n > C->L->cfg.batch) return fail(DQZ_ERR_INVALID, "n must be in [1, %d]", C->L->cfg.batch);
+  if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(DQZ_ERR_INVALID, "epsilon must be in [0, 1]");
+  const void *dstates = nullptr, *dout = nullptr;
+  if (int rc = device_view(states, &dstates, "states")) return rc;
+  if (int rc = device_view(out, &dout, "out")) return rc;
+  if (reinterpret_cast<uintptr_t>(dstates) % 16) return fail(DQZ_ERR_INVALID, "states must be 16-byte aligned");
+  Conv1Src src{nullptr, nullptr, nullptr, static_cast<const uint8_t*>(dstates), 0, UniformDraw{}};
+  return c51_forward_q(C, params, src, 0, n, C->head.qv, static_cast<dqz_action*>(const_cast<void*>(dout)), epsilon,
+                       seed, counter, (hipStream_t)stream);
+}
+
+int dqz_c51_debug_check(int batch, unsigned request) {
+  // a host-only learner, parameters and store whose pointers are set but never followed: check_step alone runs
+  static float word[4];
+  dqz_learner L{};
+  L.cfg.batch = batch;
+  L.cfg.num_actions = 6;
+  L.cfg.algo = DQZ_ALGO_DQN;
+  const dqz_params P{word, word, word, word};
+  dqz_store S{};
+  S.frames = reinterpret_cast<uint8_t*>(word);
+  S.fidx = reinterpret_cast<int32_t*>(word);
+  S.action = reinterpret_cast<int32_t*>(word);
+  S.reward = S.discount = word;
+  S.capacity = 1;
+  int32_t* iw = reinterpret_cast<int32_t*>(word);
+  UniformDraw draw{};
+  draw.slots_out = iw;
+  SoftmaxDraw sm{};
+  sm.slots_out = iw;
+  SoftmaxDrawExact smx{};
+  smx.slots_out = iw;
+  PerSampleArgs pd{};
+  pd.out_slots = iw;
+  const Rms epi{};
+  const MetaSoftmax msm{};
+  const PerWbArgs wb{};
+  const C51Head head{};
+  StepRequest r{};
+  r.slots = iw;
+  r.gout = word;
+  r.c51 = &head;
+  if (request & DQZ_C51_REQ_WEIGHTS) r.is_weights = word;
+  if (request & DQZ_C51_REQ_PER_DRAW) r.pd = &pd;
+  if (request & DQZ_C51_REQ_UNIFORM_DRAW) r.draw = &draw;
+  if (request & DQZ_C51_REQ_LOGIT_DRAW) r.sm = &sm;
+  if (request & DQZ_C51_REQ_EXACT_DRAW) r.smx = &smx;
+  if (request & DQZ_C51_REQ_META_P) r.meta_p = word;
+  if (request & DQZ_C51_REQ_META_EPI) r.meta_epi = &epi;
+  if (request & DQZ_C51_REQ_META_SOFTMAX) r.meta_sm = &msm;
+  if (request & DQZ_C51_REQ_UNIT) r.unit = 1;
+  if (request & DQZ_C51_REQ_WRITE_BACK) r.wb = &wb;
+  if (request & DQZ_C51_REQ_FUSED_RMSPROP) r.gout = nullptr;
+  return check_step(&L, &P, &S, r);
 }
 
 }  // extern "C"

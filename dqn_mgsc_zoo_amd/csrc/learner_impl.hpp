@@ -167,6 +167,24 @@ struct MetaSoftmax {
   float *x_out, *p_out;
 };
 
+// The categorical (C51) head in place of the scalar one (StepRequest::c51; c51.hpp): the learner's parameter
+// layout then ends in fc2 leaves A * N wide (c51_param_layout), the step runs in gradient mode, and the head's
+// and the fc2 gradient's launches, which live in the other code object, are made by c51_launch.
+struct C51Head {
+  int N;                 // atoms per action
+  const float* support;  // [N] device, strictly increasing
+  float* logits;         // [2][B][A N] online(s_tm1), target(s_t)
+  float* la;             // [B][N] online logits of the taken action
+  float* dl;             // [B][N] d loss / d those logits
+  float* qv;             // [2][B][A] q_values
+  int32_t* astar;        // [B] argmax_a q_values of the target copy
+};
+constexpr int C51_MAX_ATOMS = 64, C51_MAX_OUT = 1024;  // c51.hpp's C51_MAXN / C51_MAXOUT
+inline void c51_param_layout(int A, int N, int64_t off[10], int64_t sz[10], int64_t* total) {
+  param_layout(A * N, 0, off, sz, total);  // leaves 0-7 are any DQN network's; fc2 is [512, A N] + [A N]
+}
+enum C51Launch { C51_LOGITS, C51_HEAD, C51_FC2_GRAD };
+
 // What one learner step is asked to do, set by name ({.slots = ..., .gout = ...}).  Everything left out is the
 // plain step: centered RMSProp on P->online / mu / nu over the batch `slots`.
 struct StepRequest {
@@ -190,7 +208,17 @@ struct StepRequest {
   const MetaSoftmax* meta_sm;  // the head forms p itself; meta_p is then its p_out
   uint8_t* xout;               // conv1 copies sample 0's s_tm1 bytes here (Conv1Src::xout)
   PhaseEvents pe;              // dqz_learner_profile: per-phase timing instead of one pass
+  // The categorical head (C51): gradient mode only, batch from `slots`; check_step words what it refuses.
+  const C51Head* c51;
 };
+
+// One of the categorical head's three launches of a learner step (learner.hip): the logits of both copies, the
+// per-sample loss head (batch record from L->rec), the fc2 gradient into gout's fc2 leaves.
+int c51_launch(C51Launch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, void* stream);
+
+// conv1 .. fc1 forward of one network copy on n states (learner_step.hip's forward_impl, Z = 1): the fc1 split-K
+// partials are left in L->fc1p for a head of the other code object.
+int forward_torso(dqz_learner* L, const float* params, const Conv1Src& src, int which, int n, void* stream);
 
 // One learner step (learner_step.hip): check_step, what a step checks before anything is enqueued, then
 // step_enqueue, its launches.  A caller with launches of its own in front runs the two halves itself.

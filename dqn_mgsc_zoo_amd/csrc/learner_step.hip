@@ -12,9 +12,12 @@
 //     conv2 dX -> conv1 dW hand-offs, fc1 dW + fused RMSProp, conv3 / conv2
 //     dW partials                                                 bwd.hpp
 //   7 reduce of every cross-sample / split-K gradient + centered RMSProp
+// With StepRequest::c51 the categorical head's launches (c51.hpp, the other
+// code object) stand in for 4, and the fc2 gradient follows 7 in one of its own.
 // What a step is asked to do (batch source, gradient mode, PER write-back,
-// MGSC meta mode, profiling) is a StepRequest (learner_impl.hpp), whose fields
-// carry the modes' documentation; the hand-off words are named in layout.hpp.
+// MGSC meta mode, the categorical head, profiling) is a StepRequest
+// (learner_impl.hpp), whose fields carry the modes' documentation; the
+// hand-off words are named in layout.hpp.
 #define DQZ_STEP_TU 1
 #include <hip/hip_runtime.h>
 
@@ -205,6 +208,18 @@ int dqz::check_step(const dqz_learner* L, const dqz_params* P, const dqz_store* 
   if (int rc = check_store(S)) return rc;
   if (L->cfg.algo == DQZ_ALGO_PER && !r.is_weights && !r.pd) return fail(DQZ_ERR_INVALID, "PER step needs is_weights");
   if (!!r.draw + !!r.sm + !!r.smx + !!r.pd > 1) return fail(DQZ_ERR_INVALID, "a step takes at most one batch draw");
+  if (r.c51) {  // the categorical head: what it does not take, each by name
+    if (r.is_weights) return fail(DQZ_ERR_INVALID, "the categorical head takes no importance weights");
+    if (r.pd) return fail(DQZ_ERR_INVALID, "the categorical head takes no prioritized draw");
+    if (r.draw || r.sm || r.smx) return fail(DQZ_ERR_INVALID, "the categorical head takes no in-launch batch draw");
+    if (r.meta_p || r.meta_epi || r.meta_sm) return fail(DQZ_ERR_INVALID, "the categorical head has no MGSC meta mode");
+    if (r.unit) return fail(DQZ_ERR_INVALID, "the categorical head has no unit-cotangent pass");
+    if (r.wb) return fail(DQZ_ERR_INVALID, "the categorical head has no TD error to write back as a priority");
+    if (!r.gout)
+      return fail(DQZ_ERR_INVALID, "the categorical head runs in gradient mode only (no fused centered RMSProp)");
+    if (L->cfg.batch == 1) return fail(DQZ_ERR_INVALID, "the categorical head needs batch >= 2");
+    if (L->cfg.algo != DQZ_ALGO_DQN) return fail(DQZ_ERR_INVALID, "the categorical head runs on a DQN learner");
+  }
   return DQZ_OK;
 }
 
@@ -286,7 +301,14 @@ int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, c
   fb.w2 = P->online + L->off[2];
   fb.w3p = L->w3p;
   fb.w2p = L->w2p;
-  if (B == 1 && !pe.on()) {
+  if (r.c51) {
+    // the categorical head: the logits of both copies, then the per-sample loss head (c51.hpp, the other code
+    // object); behind it the backward reads dz1 as from the scalar head
+    DQZ_PHASE(4, if (int rc = c51_launch(C51_LOGITS, L, P, r, st)) return rc);
+    DQZ_PHASE(8, if (int rc = c51_launch(C51_HEAD, L, P, r, st)) return rc);
+    DQZ_PHASE(5, hipLaunchKernelGGL(fc1_dx_kernel, dim3(fc1_dx_blocks(B)), dim3(256), 0, st, fb);
+              DQZ_HIP(hipGetLastError()));
+  } else if (B == 1 && !pe.on()) {
     // one sample (the MGSC pass at theta', the HVP's unit-cotangent pass):
     // the head and fc1 dX in one launch, every block forming the head itself
     DQZ_HIP(launch_head_dx1(h, fb, st));
@@ -336,7 +358,7 @@ int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, c
   DQZ_PHASE(6, if (wb) hipLaunchKernelGGL(bwd_bc_kernel<true>, dim3(grid), dim3(256), 0, st, c3b, fb, c2b, c1dw, wbk);
             else hipLaunchKernelGGL(bwd_bc_kernel<false>, dim3(grid), dim3(256), 0, st, c3b, fb, c2b, c1dw, wbk);
             DQZ_HIP(hipGetLastError()));
-  if (pe.on()) pe.ms[7] = pe.ms[8] = 0.f;
+  if (pe.on() && !r.c51) pe.ms[7] = pe.ms[8] = 0.f;
 
   UpdArgs u{};
   u.th = P->online;
@@ -359,15 +381,23 @@ int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, c
   u.loss_part = L->loss_part;
   u.loss = L->loss;
   u.status = L->sync + sync_of(L).err();
-  u.A = A;
+  // the categorical head owns the fc2 leaves (c51_fc2_grad_kernel below): with A = nb2 = 0 the small head
+  // leaves are fc1/b alone, update_blocks counts 8 blocks for them and no range of small_grad reaches fc2
+  u.A = r.c51 ? 0 : A;
   u.B = B;
-  u.nb2 = L->shared_bias ? 1 : A;
+  u.nb2 = r.c51 ? 0 : L->shared_bias ? 1 : A;
   u.rms = rms;
   u.rms.sq_off = 4 * (FLAT / 16);  // meta_rms2 partials: the fc1 dW blocks' first, then the update's
-  const unsigned nblk = update_blocks(L->sz, A, u.nb2);
+  const unsigned nblk = update_blocks(L->sz, u.A, u.nb2);
   DQZ_PHASE(9, hipLaunchKernelGGL(update_kernel, dim3(nblk), dim3(256), 0, st, u);
             DQZ_HIP(hipGetLastError()));
+  if (r.c51) DQZ_PHASE(7, if (int rc = c51_launch(C51_FC2_GRAD, L, P, r, st)) return rc);
   return DQZ_OK;
+}
+
+int dqz::forward_torso(dqz_learner* L, const float* params, const Conv1Src& src, int which, int n, void* stream) {
+  const NetZ nz{{params, params, params}, {which, which, which}};
+  return forward_impl(L, nz, 1, n, src, (hipStream_t)stream, PhaseEvents{});
 }
 
 extern "C" {

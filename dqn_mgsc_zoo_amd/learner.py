@@ -502,6 +502,209 @@ def adam(learning_rate, b1=0.9, b2=0.999, eps=1e-8, eps_root=0.0):
   return AdamConfig(learning_rate, b1, b2, eps, eps_root)
 
 
+class C51Learner(Learner):
+  """The categorical (C51) learner: `update` of c51/agent.py:109-117 and
+  `select_action` of :121-129 on device (dqz_c51_*).
+
+  Same state surface as `Learner` (params, moments, opt_state, sync_target,
+  sync_status, grad_norm); the step is the learner step with the categorical
+  head, in gradient mode, followed by the optimizer, so the optimizer is Adam
+  or plain RMSProp, alone or behind clip_by_global_norm (the reference's chain,
+  c51/run_atari.py:210-216, is the default)."""
+
+  def __init__(self, network: networks_lib.C51NetworkSpec, batch_size,
+               optimizer=None, device='cuda'):
+    if not isinstance(network, networks_lib.C51NetworkSpec):
+      raise ValueError('C51Learner needs networks.c51_atari_network')
+    optimizer = optimizer or chain(clip_by_global_norm(10.0),
+                                   adam(2.5e-4, eps=0.01 / 32))
+    if is_centered_rmsprop(optimizer):
+      raise NotImplementedError(
+          'C51Learner applies its optimizer to the finished gradient: centered '
+          'RMSProp exists only fused into the DQN step; use adam(...), '
+          'rmsprop(..., centered=False) or chain(clip_by_global_norm(c), one '
+          'of them)')
+    self.clip_norm, base = split_optimizer(optimizer)
+    self._h = self._c51 = self._opt_h = None
+    self.network = network
+    self.algo = 'c51'
+    self.batch_size = int(batch_size)
+    self.optimizer = optimizer
+    self.base_optimizer = base
+    self.grad_error_bound = 0.0
+    self.device = torch.device(device)
+    self.offsets, self.sizes, self.total = network.layout()
+    b, a, n = self.batch_size, network.num_actions, network.num_atoms
+    f32 = dict(dtype=torch.float32, device=self.device)
+    self.online = torch.zeros((self.total,), **f32)
+    self.target = torch.zeros_like(self.online)
+    self.mu = torch.zeros_like(self.online)
+    self.nu = torch.zeros_like(self.online)
+    self.support = torch.from_numpy(network.support).to(self.device)
+    self.logits_a = torch.zeros((b, n), **f32)
+    self.q = torch.zeros((2, b, a), **f32)
+    self.loss_b = torch.zeros((b,), **f32)
+    self.loss = torch.zeros((1,), **f32)
+    self.a_star = torch.zeros((b,), dtype=torch.int32, device=self.device)
+    self.count = torch.zeros((1,), dtype=torch.int32, device=self.device)
+    self._gnorm = torch.zeros((1,), **f32)
+    lib = _native.lib()
+    cfg = _native.DqzLearnerConfig(b, a, _native.ALGO_DQN, base.learning_rate,
+                                   getattr(base, 'decay', 0.0), base.eps, 0.0)
+    handle = ctypes.c_void_p()
+    _native.check(lib.dqz_c51_create(ctypes.byref(cfg), n,
+                                     _native.ptr(self.support),
+                                     ctypes.byref(handle)))
+    self._c51 = handle
+    inner = ctypes.c_void_p()
+    _native.check(lib.dqz_c51_learner(handle, ctypes.byref(inner)))
+    self._h = inner  # owned by the c51 handle: sync_status, fetch_activations
+    is_adam = isinstance(base, AdamConfig)
+    ocfg = _native.DqzOptimizerConfig(
+        _native.OPT_ADAM if is_adam else _native.OPT_RMSPROP,
+        base.learning_rate, getattr(base, 'b1', 0.0), getattr(base, 'b2', 0.0),
+        getattr(base, 'decay', 0.0), base.eps,
+        self.clip_norm if self.clip_norm is not None else 0.0, a, 0)
+    oh = ctypes.c_void_p()
+    _native.check(lib.dqz_c51_optimizer_create(ctypes.byref(ocfg), n,
+                                               ctypes.byref(oh)))
+    self._opt_h = oh
+    self._params_c = _native.DqzParams(
+        self.online.data_ptr(), self.target.data_ptr(), self.mu.data_ptr(),
+        self.nu.data_ptr())
+
+  def __del__(self):
+    if _native is None or _native._lib is None:  # pylint: disable=protected-access
+      return
+    h = getattr(self, '_c51', None)
+    if h is not None and h.value:
+      _native.lib().dqz_c51_destroy(h)
+      self._c51 = self._h = None
+    oh = getattr(self, '_opt_h', None)
+    if oh is not None and oh.value:
+      _native.lib().dqz_optimizer_destroy(oh)
+      self._opt_h = None
+
+  def load_opt_state(self, state):
+    """Restores what opt_state() returned; a centered-RMSProp state (a DQN
+    agent's checkpoint) is refused by name."""
+    inner = state
+    if (isinstance(inner, tuple) and len(inner) == 2
+        and isinstance(inner[0], tuple) and len(inner[0]) == 0):
+      inner = inner[1]
+    first = inner[0] if isinstance(inner, tuple) and inner else None
+    fields = getattr(first, '_fields', ())  # (a tuple's own .count is a method)
+    if 'mu' in fields and 'nu' in fields and 'count' not in fields:
+      raise ValueError(
+          'a centered-RMSProp state cannot restore a C51 learner (its '
+          'optimizer is %s)' % type(self.base_optimizer).__name__)
+    super().load_opt_state(state)
+
+  def _check_slots(self, slots):
+    if slots.dtype != torch.int32 or slots.numel() != self.batch_size:
+      raise ValueError('slots must be a device int32 tensor of batch size')
+
+  def step(self, store, slots, stream=None):  # pylint: disable=arguments-differ
+    """One learner step on replay `slots` (device int32 [B])."""
+    self._check_slots(slots)
+    _native.check(_native.lib().dqz_c51_step(
+        self._c51, ctypes.byref(self._params_c), store.c_ref(),
+        _native.ptr(slots), self._opt_h, _native.ptr(self.count),
+        _native.stream_handle(stream)))
+
+  def grad(self, store, slots, out=None, stream=None):  # pylint: disable=arguments-differ
+    """jax.grad(loss_fn) of the same step into a flat tensor (no update)."""
+    self._check_slots(slots)
+    out = torch.zeros_like(self.online) if out is None else out
+    _native.check(_native.lib().dqz_c51_grad(
+        self._c51, ctypes.byref(self._params_c), store.c_ref(),
+        _native.ptr(slots), _native.ptr(out), _native.stream_handle(stream)))
+    return out
+
+  def fetch_outputs(self, stream=None):
+    """(logits of the taken action [B,N], q_values [2,B,A] of online(s_tm1)
+    and target(s_t), per-sample loss [B], mean loss [1], the target's greedy
+    action [B]) of the last step, copied into self tensors."""
+    _native.check(_native.lib().dqz_c51_outputs(
+        self._c51, _native.ptr(self.logits_a), _native.ptr(self.q),
+        _native.ptr(self.loss_b), _native.ptr(self.loss),
+        _native.ptr(self.a_star), _native.stream_handle(stream)))
+    return self.logits_a, self.q, self.loss_b, self.loss, self.a_star
+
+  def fetch_head(self, stream=None):
+    """Diagnostic: the last step's q_logits [2,B,A,N] and dlogits [B,N]."""
+    b, a, n = self.batch_size, self.network.num_actions, self.network.num_atoms
+    logits = torch.empty((2, b, a, n), dtype=torch.float32, device=self.device)
+    dlogits = torch.empty((b, n), dtype=torch.float32, device=self.device)
+    _native.check(_native.lib().dqz_c51_debug(
+        self._c51, _native.ptr(logits), _native.ptr(dlogits),
+        _native.stream_handle(stream)))
+    return logits, dlogits
+
+  def profile(self, store, slots, iters=20, stream=None):  # pylint: disable=arguments-differ
+    """Average ms per launch (dqz_c51_profile), dict; the gradient goes to a
+    scratch tensor and no parameter changes."""
+    self._check_slots(slots)
+    out = (ctypes.c_float * _native.NUM_PHASES)()
+    scratch = torch.zeros_like(self.online)
+    _native.check(_native.lib().dqz_c51_profile(
+        self._c51, ctypes.byref(self._params_c), store.c_ref(),
+        _native.ptr(slots), _native.ptr(scratch), int(iters), out,
+        _native.stream_handle(stream)))
+    names = list(_native.PHASE_NAMES)
+    names[4], names[8], names[7] = 'c51_logits', 'c51_head', 'c51_fc2_grad'
+    return {n: float(t) for n, t in zip(names, out) if t > 0.0}
+
+  def q_values(self, states, params=None, stream=None):
+    """network.apply(params, s).q_values for uint8 [n,84,84,4] device states."""
+    params = self.online if params is None else params
+    states = states.contiguous()
+    n = int(states.shape[0])
+    out = torch.empty((n, self.network.num_actions), dtype=torch.float32,
+                      device=self.device)
+    for i in range(0, n, self.batch_size):
+      j = min(n, i + self.batch_size)
+      _native.check(_native.lib().dqz_c51_forward(
+          self._c51, _native.ptr(params), _native.ptr(states[i:j]), j - i,
+          _native.ptr(out[i:j]), _native.stream_handle(stream)))
+    return out
+
+  def q_values_slots(self, store, slots, which, params=None, stream=None):
+    params = self.online if params is None else params
+    n = int(slots.numel())
+    out = torch.empty((n, self.network.num_actions), dtype=torch.float32,
+                      device=self.device)
+    _native.check(_native.lib().dqz_c51_forward_slots(
+        self._c51, _native.ptr(params), store.c_ref(), _native.ptr(slots), n,
+        int(which), _native.ptr(out), _native.stream_handle(stream)))
+    return out
+
+  def act(self, observation, epsilon, seed, counter, params=None):
+    """select_action on device (c51/agent.py:121-129): (action, max_a
+    q_values), as Learner.act."""
+    if getattr(self, '_act_in', None) is None:
+      self._act_in = torch.empty((1, 84, 84, 4), dtype=torch.uint8,
+                                 pin_memory=True)
+      self._act_in_np = self._act_in.numpy()
+      self._act_out = torch.zeros((2,), dtype=torch.int32, pin_memory=True)
+      self._act_out_np = self._act_out.numpy()
+    self._act_in_np[0] = observation
+    _native.check(_native.lib().dqz_c51_act(
+        self._c51, _native.ptr(self._params_tensor(params)),
+        ctypes.c_void_p(self._act_in.data_ptr()), 1, float(epsilon),
+        int(seed) & (2**64 - 1), int(counter) & (2**64 - 1),
+        ctypes.c_void_p(self._act_out.data_ptr()), _native.stream_handle()))
+    torch.cuda.current_stream(self.device).synchronize()
+    return int(self._act_out_np[0]), float(self._act_out_np.view(np.float32)[1])
+
+  def _no_fused_draw(self, *unused_args, **unused_kwargs):
+    raise NotImplementedError(
+        'the categorical step takes its batch as slots: sample them first '
+        '(replay.sample_slots) and call step')
+
+  step_uniform = step_logits = step_per_draw = _no_fused_draw
+
+
 class MetaLearner:
   """MGSC meta-update on device (dqn_mgsc_batched/agent.py:104-220, 302-334).
 

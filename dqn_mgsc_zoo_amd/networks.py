@@ -156,3 +156,38 @@ def dqn_atari_network(num_actions: int) -> NetworkSpec:
 def double_dqn_atari_network(num_actions: int) -> NetworkSpec:
   """DQN network with shared bias in the final layer (networks.py:338-349)."""
   return NetworkSpec(num_actions=int(num_actions), shared_bias=True)
+
+
+class C51NetworkOutputs(typing.NamedTuple):
+  q_logits: typing.Any
+  q_values: typing.Any
+
+
+class C51NetworkSpec(NetworkSpec):
+  """NetworkSpec of the categorical network: `dqn_atari_network`'s leaf names
+  with `linear_1` [512, A * N] wide, plus the fixed support (float32 [N],
+  strictly increasing) and its length `num_atoms`.
+  q_logits[b, a, j] = out[b, a * N + j]."""
+
+  def __new__(cls, num_actions, support):
+    support = np.asarray(support, dtype=np.float32).reshape(-1)
+    if support.size < 2:
+      raise ValueError('num_atoms < 2: the support needs at least two atoms')
+    if not (np.all(np.isfinite(support)) and np.all(np.diff(support) > 0)):
+      raise ValueError('support must be finite and strictly increasing')
+    self = super().__new__(cls, int(num_actions), False)
+    self.support = support
+    self.num_atoms = int(support.size)
+    return self
+
+  def leaf_shapes(self):
+    outputs = self.num_actions * self.num_atoms
+    return [shape_fn(outputs) for _, _, shape_fn, _ in _LEAVES]
+
+  def layout(self):
+    return _native.c51_param_layout(self.num_actions, self.num_atoms)
+
+
+def c51_atari_network(num_actions: int, support) -> C51NetworkSpec:
+  """C51 network, expects uint8 input (networks.py:316-335)."""
+  return C51NetworkSpec(num_actions, support)

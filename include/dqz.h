@@ -638,6 +638,100 @@ int dqz_learner_step_opt_uniform(dqz_learner* learner, const dqz_params* params,
 int dqz_learner_step_opt_per_draw(dqz_learner* learner, const dqz_params* params, const dqz_store* store,
                                   const dqz_per_draw* draw, dqz_optimizer* opt, int32_t* count, void* stream);
 
+/* ---- the categorical (C51) agent (c51/agent.py:36-39,87-129) --------------
+ * networks.c51_atari_network (networks.py:316-335): the NatureQNetwork torso
+ * with a last layer A * N wide, N atoms per action on a fixed support z [N]
+ * (strictly increasing; never recomputed on the device, no kernel assumes
+ * equal spacing):
+ *   q_logits[b, a, j] = out[b, a N + j];  q_values[b, a] = sum_j softmax_j z_j.
+ * Loss (rlax 0.1.2 categorical_q_learning), per sample: P = softmax of the
+ * target logits at s_t, a* = argmax_a sum_j P[a, j] z_j (first maximum),
+ * p = P[a*], y_i = clip(r + d z_i, z_0, z_{N-1}), m = categorical_l2_project
+ * of (y, p) onto z, loss_b = -sum_k m_k log_softmax(l)_k with l the online
+ * logits of the taken action; the step's loss is the batch mean, and
+ * d loss / d l_k = (softmax(l)_k - m_k) / B.  No clip_gradient, no TD error,
+ * no importance weights.
+ * The parameter layout is dqz_param_layout's with leaves 8 and 9 widened:
+ *   8 linear_1/w [512, A N]   9 linear_1/b [A N]
+ * 2 <= N <= 64 and A N <= 1024 (18 actions x 51 atoms = 918 fit). */
+int dqz_c51_param_layout(int num_actions, int num_atoms, int64_t offsets[DQZ_NUM_LEAVES],
+                         int64_t sizes[DQZ_NUM_LEAVES], int64_t* total);
+
+/* dqz_optimizer_create for that layout (cfg->num_actions = A, shared_bias 0). */
+int dqz_c51_optimizer_create(const dqz_optimizer_config* cfg, int num_atoms, dqz_optimizer** out);
+
+typedef struct dqz_c51 dqz_c51;
+
+/* A learner on the categorical layout plus the head's buffers.  cfg: batch
+ * 2..256, num_actions, algo DQZ_ALGO_DQN; its optimizer fields and
+ * grad_error_bound are unused.  support: device f32 [num_atoms], copied (and
+ * checked on the host: this call synchronises). */
+int dqz_c51_create(const dqz_learner_config* cfg, int num_atoms, const float* support, dqz_c51** out);
+int dqz_c51_destroy(dqz_c51* c51);
+
+/* The dqz_learner inside (owned by the handle): dqz_learner_sync_status and
+ * dqz_learner_debug_activations apply to it; its q stays unused. */
+int dqz_c51_learner(dqz_c51* c51, dqz_learner** out);
+
+/* One jitted `update` (c51/agent.py:109-117): the learner step's forward with
+ * the categorical head in place of the scalar one, its backward in gradient
+ * mode into the optimizer's scratch, the fc2 gradient, then
+ * dqz_optimizer_apply on params->online / mu / nu and `count`.  slots: device
+ * int32 [B].  Same stream, no allocation, no host synchronisation, capturable
+ * in a graph.  The learner's health word keeps its meaning (bit 1: a
+ * non-finite batch loss). */
+int dqz_c51_step(dqz_c51* c51, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                 dqz_optimizer* opt, int32_t* count, void* stream);
+
+/* Gradient only (jax.grad(loss_fn)) into grad_out, dqz_c51_param_layout
+ * order, padding untouched; mu / nu may be NULL. */
+int dqz_c51_grad(dqz_c51* c51, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                 float* grad_out, void* stream);
+
+/* Device-to-device copies of the last step's outputs (any may be NULL):
+ * logits_a [B][N] online logits of the taken action, q_values [2][B][A]
+ * (online at s_tm1, target at s_t), loss_b [B] per-sample loss, loss [1] their
+ * mean, a_star int32 [B] the target's greedy action. */
+int dqz_c51_outputs(dqz_c51* c51, float* logits_a, float* q_values, float* loss_b, float* loss,
+                    int32_t* a_star, void* stream);
+
+/* Diagnostic (tests): the last step's full logits [2][B][A N] and
+ * dlogits [B][N] (either may be NULL). */
+int dqz_c51_debug(dqz_c51* c51, float* logits, float* dlogits, void* stream);
+
+/* dqz_learner_profile of the categorical step (gradient mode into grad_out):
+ * phases 0, 3, 5, 6, 9 as there (9 without the fc2 leaves), 4 the logits
+ * launch, 8 the per-sample loss head, 7 the fc2 gradient. */
+int dqz_c51_profile(dqz_c51* c51, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                    float* grad_out, int iters, float* phase_ms, void* stream);
+
+/* q_values [n][A] of uint8 states / replay slots, and select_action
+ * (c51/agent.py:121-129): dqz_forward, dqz_forward_slots and dqz_act on the
+ * categorical network; out[i].value = max_a q_values. */
+int dqz_c51_forward(dqz_c51* c51, const float* params, const uint8_t* states, int n, float* q_out,
+                    void* stream);
+int dqz_c51_forward_slots(dqz_c51* c51, const float* params, const dqz_store* store, const int32_t* slots,
+                          int n, int which, float* q_out, void* stream);
+int dqz_c51_act(dqz_c51* c51, const float* params, const uint8_t* states, int n, double epsilon,
+                uint64_t seed, uint64_t counter, dqz_action* out, void* stream);
+
+/* Diagnostic (tests): what the learner step checks of a categorical request,
+ * on host structures only (no device call): a request on `slots` in gradient
+ * mode at batch `batch`, plus the modes named by `request`; returns the
+ * step's own status and message. */
+#define DQZ_C51_REQ_WEIGHTS 1u        /* PER importance weights */
+#define DQZ_C51_REQ_PER_DRAW 2u       /* the fused prioritized draw */
+#define DQZ_C51_REQ_UNIFORM_DRAW 4u   /* in-launch draws */
+#define DQZ_C51_REQ_LOGIT_DRAW 8u
+#define DQZ_C51_REQ_EXACT_DRAW 16u
+#define DQZ_C51_REQ_META_P 32u        /* MGSC meta modes */
+#define DQZ_C51_REQ_META_EPI 64u
+#define DQZ_C51_REQ_META_SOFTMAX 128u
+#define DQZ_C51_REQ_UNIT 256u         /* the HVP's unit cotangent */
+#define DQZ_C51_REQ_WRITE_BACK 512u   /* the fused PER write-back */
+#define DQZ_C51_REQ_FUSED_RMSPROP 1024u /* no gradient output: the fused centered RMSProp */
+int dqz_c51_debug_check(int batch, unsigned request);
+
 /* PrioritizedTransitionReplay.add on device (replay.py:1068-1096 ->
  * PrioritizedDistribution.remove_priorities / add_priorities, :642-678): the
  * evicted tree index remove_index (-1: none) is set to 0, add_index to

@@ -1,0 +1,517 @@
+"""GPU: the categorical (C51) learner step, actor and agent (csrc/c51.hpp,
+dqz_c51_*) against tests/c51_ref.py (float64).
+
+Store: tests/test_learner_gpu.py's (capacity 256, 640 frames), rewards in
+{-1, 0, 1}, a tenth of the discounts 0, with two edits: the last action is
+never taken (so every batch has an absent action), and one slot's reward is
+2 vmax + 1, which puts every y_i = r + d z_i beyond z_{N-1}; that slot is in
+every single-step batch.  Each batch also has a zero discount and an action
+taken at least twice, and every test asserts, in float64 on the CPU, that each
+sample's best-versus-second q_values margin at the target is >= 1e-3 (the seeds
+below were chosen for that), so the greedy action a* is not a rounding matter.
+
+Stage checks, from the device's own inputs (u = 2^-24, N atoms, zmax = max|z|,
+dz = the smallest atom spacing, D = the largest logit-minus-row-maximum the
+device's logits hold, rmax = max |r|).  In float32, from the same logits:
+  softmax       each exp carries its argument's rounding (D u) and expf's own
+                (<= 2 u); the N-term sum adds (N - 1) u, the division u:
+                rel(p) <= (N + 2 D + 6) u.
+  q_values      sum_j p_j z_j with sum_j p_j |z_j| <= zmax and an N-term sum:
+                |dq| <= zmax (rel(p) + (N + 1) u).
+  projection    y = fma(d, z_i, r) is rounded once before the (exact) clip:
+                u (rmax + zmax); y - z_k and the product with the reciprocal
+                spacing add 3 u zmax / dz: each weight w_ki in [0, 1] is within
+                dw = u (rmax + 4 zmax) / dz + 3 u; at most three atoms take
+                part of any y_i, so sum_k |dm_k| <= 3 dw + rel(p) + N u =: sm,
+                and |dm_k| is bounded by the same figure.
+  loss_b        log_softmax is within lp = (D + 2 ln N + N + 4) u, |log p| <=
+                D + ln N: |dloss_b| <= sm (D + ln N) + lp + N u (D + ln N).
+  dlogits       (softmax - m) / B: |d| <= (rel(p) + sm + 2 u) / B.
+  dz1, dW2, db2 fma chains of N (dz1) or at most B (fc2) terms: per element
+                (terms + 1) u sum |term|, from the device's own h1 and dlogits.
+The fc2 product itself (the device's h1 through a float64 fc2) is held to atol
+1e-5, as the issue sets.
+
+End to end (kink-free batches, or the device's ReLU masks and a* pinned in the
+oracle for the carried steps): logits atol 1e-4, q_values atol 1e-4 zmax, mean
+loss rtol 1e-4 (|dloss| <= 2 max|dlogit| against a loss near ln N), and after
+one chain(clip_by_global_norm(10), adam) step tests/test_optimizers_gpu.py's
+bars: params atol 2e-6, moments rtol 1e-3 with atol 2e-9 (m) and 1e-12 (v),
+grad_norm rtol 1e-4.
+"""
+
+import copy
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import learner_ref
+from tests import c51_ref
+from tests import fake_env
+from tests import helpers
+from tests.test_trajectory_gpu import _batch
+
+pytestmark = pytest.mark.gpu
+
+LR, ADAM_EPS, B1, B2, CLIP = 2.5e-4, 0.01 / 32, 0.9, 0.999, 10.0  # c51/run_atari.py:80-81, 210-216
+VMAX = 10.0
+U = 2.0**-24
+MARGIN = 1e-3
+SPECIAL = 7  # the slot whose reward clips every y_i to the last atom
+# (B, A, N) -> seed; chosen on the CPU for the margin (and the kink-free draw)
+SHAPES = {(8, 6, 51): 2, (32, 6, 51): 3, (5, 3, 7): 1, (8, 18, 51): 1}
+SHAPE_IDS = ['%dx%dx%d' % s for s in SHAPES]
+
+
+def _f32(x):
+  return float(np.float32(x))
+
+
+def _optimizer(clip=CLIP):
+  from dqn_mgsc_zoo_amd import learner as learner_lib
+  opt = learner_lib.adam(LR, B1, B2, ADAM_EPS)
+  return opt if clip is None else learner_lib.chain(learner_lib.clip_by_global_norm(clip), opt)
+
+
+def _margin(q):
+  s = np.sort(np.asarray(q, np.float64), axis=1)
+  return float((s[:, -1] - s[:, -2]).min())
+
+
+def _store_contents(a, seed):
+  frames, fidx, action, reward, discount = helpers.random_store_contents(256, 640, a, seed + 3)
+  action[action == a - 1] = 0
+  reward[SPECIAL] = 2 * VMAX + 1
+  discount[SPECIAL] = 0.99
+  return dict(frames=frames, fidx=fidx, action=action, reward=reward, discount=discount)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(b, a, n):
+  """Host side of one shape, computed once: parameters, store contents, a
+  kink-free batch meeting the input conditions, and the oracle's step from
+  zero moments.  Nothing in it is modified by the tests."""
+  from dqn_mgsc_zoo_amd import networks
+  seed = SHAPES[(b, a, n)]
+  support = c51_ref.make_support(VMAX, n)
+  net = networks.c51_atari_network(a, support)
+  online = net.init(seed)
+  target = helpers.perturbed_tree(online, seed + 1)
+  host = _store_contents(a, seed)
+  rng = np.random.default_rng(seed + 5)
+  for _ in range(400):
+    slots = rng.integers(0, 256, size=b).astype(np.int32)
+    slots[0] = SPECIAL
+    counts = np.bincount(host['action'][slots], minlength=a)
+    if not (host['discount'][slots] == 0).any() or counts.max() < 2:
+      continue
+    if learner_ref.relu_margin(online, helpers.stacks_from(host['frames'], host['fidx'], slots, 0)) >= 1e-6:
+      break
+  else:
+    raise AssertionError('no batch meets the input conditions')
+  zeros = learner_ref.zeros_like_tree(online)
+  ref = c51_ref.learner_step(online, target, zeros, zeros, 0, _batch(host, slots), support, a,
+                             _f32(LR), _f32(B1), _f32(B2), _f32(ADAM_EPS), clip=_f32(CLIP))
+  return dict(net=net, support=support, online=online, target=target, host=host, slots=slots, ref=ref,
+              zeros=zeros)
+
+
+def _check_conditions(case, ref=None, slots=None, single=True):
+  ref = case['ref'] if ref is None else ref
+  slots = case['slots'] if slots is None else slots
+  host = case['host']
+  margin = _margin(ref['q_target_t'])
+  print('target q_values margin %.3e' % margin)
+  assert margin >= MARGIN
+  assert set(np.unique(host['reward'][np.arange(256) != SPECIAL])) <= {-1.0, 0.0, 1.0}
+  if single:
+    counts = np.bincount(host['action'][slots], minlength=case['net'].num_actions)
+    assert counts.min() == 0 and counts.max() >= 2 and (host['discount'][slots] == 0).any()
+    z = case['support'].astype(np.float64)
+    i = list(slots).index(SPECIAL)
+    assert (host['reward'][SPECIAL] + host['discount'][SPECIAL] * z >= z[-1]).all()
+    assert ref['m'][i][-1] == pytest.approx(1.0, abs=1e-12)
+
+
+def _device(case, device, batch=None, clip=CLIP):
+  from dqn_mgsc_zoo_amd import learner as learner_lib
+  from dqn_mgsc_zoo_amd import store as store_lib
+  lrn = learner_lib.C51Learner(case['net'], len(case['slots']) if batch is None else batch,
+                               optimizer=_optimizer(clip), device=device)
+  lrn.set_params(case['online'], case['target'])
+  st = store_lib.FrameStore(256, 640)
+  for name, arr in case['host'].items():
+    getattr(st, name).copy_(torch.from_numpy(arr))
+  return lrn, st
+
+
+def _compare_tree(got, want, atol, rtol=0.0, what=''):
+  for m in want:
+    for n in want[m]:
+      np.testing.assert_allclose(got[m][n], want[m][n], atol=atol, rtol=rtol,
+                                 err_msg='%s %s/%s' % (what, m, n))
+
+
+def _np(t):
+  return t.detach().cpu().numpy()
+
+
+def _bits(t):
+  return _np(t).view(np.int32).copy()
+
+
+def _within(got, want, bound, what):
+  err = np.abs(np.asarray(got, np.float64) - want)
+  bound = np.broadcast_to(np.asarray(bound, np.float64), err.shape)
+  worst = int(np.argmax(err / np.maximum(bound, 1e-300)))
+  print('%s: err / bound at most %.3f (err %.3e, bound %.3e)' % (
+      what, err.flat[worst] / max(bound.flat[worst], 1e-300), err.flat[worst], bound.flat[worst]))
+  assert (err <= bound).all(), (what, worst, err.flat[worst], bound.flat[worst])
+
+
+@pytest.mark.parametrize('shape', list(SHAPES), ids=SHAPE_IDS)
+def test_stages_from_the_devices_own_inputs(device, shape):
+  b, a, n = shape
+  case = _case(*shape)
+  _check_conditions(case)
+  lrn, st = _device(case, device)
+  host, slots, z = case['host'], case['slots'], case['support'].astype(np.float64)
+  g = lrn.grad(st, torch.from_numpy(slots).to(device))
+  logits_a, qv, loss_b, loss, a_star = [_np(x) for x in lrn.fetch_outputs()]
+  logits, dl = [_np(x) for x in lrn.fetch_head()]
+  act0 = lrn.fetch_activations(0, backward=True)
+  h1 = [_np(act0['h1']).astype(np.float64), _np(lrn.fetch_activations(1)['h1']).astype(np.float64)]
+  dz1 = _np(act0['dz1'])
+  assert lrn.sync_status() == 0
+  head = 'sequential/sequential_1/linear_1'
+  # fc2: the device's h1 through a float64 fc2
+  for zc, tree in enumerate((case['online'], case['target'])):
+    want = h1[zc] @ tree[head]['w'].astype(np.float64) + tree[head]['b'].astype(np.float64)
+    np.testing.assert_allclose(logits[zc].reshape(b, -1), want, atol=1e-5, err_msg='logits of copy %d' % zc)
+  # everything behind the logits, from the device's logits
+  acts, r, d = host['action'][slots], host['reward'][slots], host['discount'][slots]
+  ref = c51_ref.categorical_loss(logits[0], acts, r, d, logits[1], z)
+  assert _margin(ref['q_target_t']) >= MARGIN
+  dmax = float((logits.max(axis=-1, keepdims=True) - logits).max())
+  zmax, dz, rmax = float(np.abs(z).max()), float(np.diff(z).min()), float(np.abs(r).max())
+  rel_p = (n + 2 * dmax + 6) * U
+  dw = U * (rmax + 4 * zmax) / dz + 3 * U
+  sm = 3 * dw + rel_p + n * U
+  lp = (dmax + 2 * np.log(n) + n + 4) * U
+  print('D %.3f: rel(p) %.2e, dw %.2e, sum|dm| %.2e' % (dmax, rel_p, dw, sm))
+  np.testing.assert_array_equal(a_star, ref['a_star'])
+  np.testing.assert_array_equal(logits_a, logits[0][np.arange(b), acts])
+  _within(qv[0], ref['q_tm1'], zmax * (rel_p + (n + 1) * U), 'q_values online')
+  _within(qv[1], ref['q_target_t'], zmax * (rel_p + (n + 1) * U), 'q_values target')
+  _within(loss_b, ref['loss_b'], sm * (dmax + np.log(n)) + lp + n * U * (dmax + np.log(n)), 'loss_b')
+  _within(dl, ref['dl'], (rel_p + sm + 2 * U) / b, 'dlogits')
+  _within(loss[0], np.mean(loss_b.astype(np.float64)), (b + 1) * U * np.abs(loss_b).mean(), 'mean loss')
+  # dz1 and the fc2 gradient leaves, from the device's h1 and dlogits
+  w2 = case['online'][head]['w'].astype(np.float64).reshape(512, a, n)
+  dl64 = dl.astype(np.float64)
+  wa = w2[:, acts, :].transpose(1, 0, 2)  # [B, 512, N]
+  mask = h1[0] > 0
+  _within(dz1, np.einsum('bk,bjk->bj', dl64, wa) * mask,
+          (n + 1) * U * np.einsum('bk,bjk->bj', np.abs(dl64), np.abs(wa)) + 1e-45, 'dz1')
+  onehot = (acts[:, None] == np.arange(a)[None, :]).astype(np.float64)  # [B, A]
+  gw = np.einsum('bj,ba,bk->jak', h1[0], onehot, dl64).reshape(512, a * n)
+  gw_abs = np.einsum('bj,ba,bk->jak', np.abs(h1[0]), onehot, np.abs(dl64)).reshape(512, a * n)
+  gb = np.einsum('ba,bk->ak', onehot, dl64).reshape(-1)
+  gb_abs = np.einsum('ba,bk->ak', onehot, np.abs(dl64)).reshape(-1)
+  got = case['net'].unflatten(_np(g))
+  _within(got[head]['w'], gw, (b + 1) * U * gw_abs + 1e-45, 'dW2')
+  _within(got[head]['b'], gb, (b + 1) * U * gb_abs + 1e-45, 'db2')
+  absent = np.flatnonzero(onehot.sum(0) == 0)
+  assert absent.size >= 1
+  for aa in absent:  # exactly 0.0 for an action the batch does not take
+    assert not got[head]['w'][:, aa * n:(aa + 1) * n].view(np.int32).any()
+    assert not got[head]['b'][aa * n:(aa + 1) * n].view(np.int32).any()
+  # every element of both leaves is written: a second call into a poisoned buffer gives the same bytes
+  g2 = torch.full_like(g, float('nan'))
+  lrn.grad(st, torch.from_numpy(slots).to(device), out=g2)
+  offs, sizes, _ = case['net'].layout()
+  for o, s in zip(offs, sizes):
+    assert torch.equal(g[o:o + s].view(torch.int32), g2[o:o + s].view(torch.int32))
+
+
+def _check_step(lrn, ref, what, head=None):
+  """One device step against c51_ref.learner_step's result `ref`."""
+  logits_a, qv, loss_b, loss, a_star = [_np(x) for x in lrn.fetch_outputs()]
+  zmax = float(np.abs(lrn.network.support).max())
+  np.testing.assert_array_equal(a_star, ref['a_star'])
+  np.testing.assert_allclose(logits_a, ref['logits_a'], atol=1e-4, err_msg=what)
+  if head is not None:
+    np.testing.assert_allclose(head[1], ref['logits_target_t'], atol=1e-4, err_msg=what)
+  np.testing.assert_allclose(qv[0], ref['q_tm1'], atol=1e-4 * zmax, err_msg=what)
+  np.testing.assert_allclose(qv[1], ref['q_target_t'], atol=1e-4 * zmax, err_msg=what)
+  np.testing.assert_allclose(loss[0], ref['loss'], rtol=1e-4, err_msg=what)
+  np.testing.assert_allclose(float(lrn.grad_norm().item()), ref['grad_norm'], rtol=1e-4, err_msg=what)
+  assert int(lrn.count.item()) == ref['count']
+  _compare_tree(lrn.params_tree('online'), ref['params'], 2e-6, what=what + ' params')
+  _compare_tree(lrn.params_tree('mu'), ref['mu'], 2e-9, 1e-3, what=what + ' m')
+  _compare_tree(lrn.params_tree('nu'), ref['nu'], 1e-12, 1e-3, what=what + ' v')
+
+
+@pytest.mark.parametrize('shape', list(SHAPES), ids=SHAPE_IDS)
+def test_one_step_matches_the_oracle(device, shape):
+  case = _case(*shape)
+  _check_conditions(case)
+  lrn, st = _device(case, device)
+  lrn.step(st, torch.from_numpy(case['slots']).to(device))
+  head = [_np(x) for x in lrn.fetch_head()][0]
+  _check_step(lrn, case['ref'], 'x'.join(map(str, shape)), head)
+  _compare_tree(lrn.params_tree('target'), case['target'], 0.0, what='target')
+  assert lrn.sync_status() == 0
+  print('loss %.6f (ln N = %.6f), gradient norm %.4f' % (case['ref']['loss'], np.log(shape[2]),
+                                                          case['ref']['grad_norm']))
+
+
+TRAJ_SEED = 21  # the ten batches' draws; chosen on the CPU for the margin on every step
+
+
+def test_ten_carried_steps(device):
+  """tests/test_trajectory_gpu.py's manner: every step the oracle starts from
+  the device's own state, with the device's ReLU masks and a*; unfiltered
+  batches; a target sync after step 5, bit-equal."""
+  shape = (8, 6, 51)
+  case = _case(*shape)
+  lrn, st = _device(case, device)
+  rng = np.random.default_rng(TRAJ_SEED)
+  hp = [_f32(x) for x in (LR, B1, B2, ADAM_EPS)]
+  for step in range(10):
+    slots = rng.integers(0, 256, size=shape[0]).astype(np.int32)
+    torch.cuda.synchronize()
+    state = [lrn.params_tree(w) for w in ('online', 'target', 'mu', 'nu')]
+    count = int(lrn.count.item())
+    lrn.step(st, torch.from_numpy(slots).to(device))
+    act = lrn.fetch_activations(0)
+    masks = [_np(act[k]) > 0 for k in ('y1', 'y2', 'y3', 'h1')]
+    a_star = _np(lrn.fetch_outputs()[4])
+    ref = c51_ref.learner_step(state[0], state[1], state[2], state[3], count, _batch(case['host'], slots),
+                               case['support'], shape[1], *hp, clip=_f32(CLIP), masks=masks, select=a_star)
+    _check_conditions(case, ref, slots, single=False)
+    np.testing.assert_array_equal(a_star, np.argmax(ref['q_target_t'], axis=1))
+    _check_step(lrn, ref, 'step %d' % step, [_np(x) for x in lrn.fetch_head()][0])
+    if step == 5:
+      lrn.sync_target()
+      torch.cuda.synchronize()
+      assert torch.equal(lrn.online.view(torch.int32), lrn.target.view(torch.int32))
+  assert int(lrn.count.item()) == 10 and lrn.sync_status() == 0
+
+
+def _snapshot(lrn):
+  return [t.clone() for t in (lrn.online, lrn.mu, lrn.nu, lrn.count)]
+
+
+def _restore(lrn, snap):
+  for t, s in zip((lrn.online, lrn.mu, lrn.nu, lrn.count), snap):
+    t.copy_(s)
+
+
+def _all_bits(lrn):
+  out = [_bits(t) for t in (lrn.online, lrn.mu, lrn.nu, lrn.count, lrn.target)]
+  out += [_bits(t) for t in lrn.fetch_outputs()]
+  out += [_bits(t) for t in lrn.fetch_head()]
+  out.append(_bits(lrn.grad_norm()))
+  return out
+
+
+def test_a_step_is_bit_reproducible(device):
+  case = _case(8, 6, 51)
+  lrn, st = _device(case, device)
+  slots = torch.from_numpy(case['slots']).to(device)
+  lrn.step(st, slots)  # carried moments under the repeated step
+  snap = _snapshot(lrn)
+  runs = []
+  for _ in range(2):
+    _restore(lrn, snap)
+    lrn.step(st, slots)
+    torch.cuda.synchronize()
+    runs.append(_all_bits(lrn))
+  for x, y in zip(*runs):
+    assert np.array_equal(x, y)
+  assert not np.array_equal(runs[0][0], _bits(snap[0]))
+
+
+def test_three_captured_steps_equal_three_eager_steps(device):
+  case = _case(8, 6, 51)
+  lrn, st = _device(case, device)
+  slots = torch.from_numpy(case['slots']).to(device)
+  snap = _snapshot(lrn)
+  for _ in range(3):
+    lrn.step(st, slots)
+  torch.cuda.synchronize()
+  eager = _all_bits(lrn)
+  side = torch.cuda.Stream(device)
+  side.wait_stream(torch.cuda.current_stream(device))
+  with torch.cuda.stream(side):  # warm-up off the default stream, as capture requires
+    lrn.step(st, slots)
+  torch.cuda.current_stream(device).wait_stream(side)
+  g = torch.cuda.CUDAGraph()
+  with torch.cuda.graph(g):
+    for _ in range(3):
+      lrn.step(st, slots)
+  torch.cuda.synchronize()
+  _restore(lrn, snap)
+  g.replay()
+  torch.cuda.synchronize()
+  for x, y in zip(eager, _all_bits(lrn)):
+    assert np.array_equal(x, y)
+  assert int(lrn.count.item()) == 3
+
+
+def test_dqn_step_unchanged_beside_a_c51_learner(device):
+  """One Learner(algo='dqn') step before and after a C51 learner has run in
+  the same process: identical bytes."""
+  from tests.test_learner_gpu import _setup
+  def dqn_step():
+    _, lrn, st, host, _, _, _, _ = _setup('dqn', 8, seed=3)
+    slots = torch.from_numpy(np.random.default_rng(5).integers(0, 256, 8).astype(np.int32)).to(device)
+    lrn.step(st, slots)
+    torch.cuda.synchronize()
+    return [_bits(t) for t in (lrn.online, lrn.mu, lrn.nu) + tuple(lrn.fetch_outputs())]
+  before = dqn_step()
+  case = _case(8, 6, 51)
+  c51, st = _device(case, device)
+  c51.step(st, torch.from_numpy(case['slots']).to(device))
+  c51.q_values_slots(st, torch.from_numpy(case['slots']).to(device), 0)
+  torch.cuda.synchronize()
+  for x, y in zip(before, dqn_step()):
+    assert np.array_equal(x, y)
+
+
+def test_actor(device):
+  shape = (8, 6, 51)
+  case = _case(*shape)
+  lrn, st = _device(case, device)
+  host, slots, z = case['host'], case['slots'], case['support']
+  s_t = helpers.stacks_from(host['frames'], host['fidx'], slots, 1)
+  out, _ = learner_ref.forward(case['online'], s_t)
+  q_ref = c51_ref.q_values(out.reshape(len(slots), shape[1], shape[2]), z)
+  assert _margin(q_ref) >= MARGIN
+  zmax = float(np.abs(z).max())
+  q_direct = lrn.q_values(torch.from_numpy(s_t).to(device))
+  q_slots = lrn.q_values_slots(st, torch.from_numpy(slots).to(device), 1)
+  np.testing.assert_allclose(_np(q_direct), q_ref, atol=1e-4 * zmax)
+  assert torch.equal(q_direct, q_slots)
+  q1 = lrn.q_values(torch.from_numpy(s_t[2:3]).to(device))  # n below the batch
+  np.testing.assert_allclose(_np(q1), q_ref[2:3], atol=1e-4 * zmax)
+  for i in range(3):  # greedy: argmax q_values, state_value = max_a q_values
+    action, value = lrn.act(s_t[i], 0.0, seed=9, counter=i)
+    assert action == int(np.argmax(q_ref[i]))
+    assert abs(value - q_ref[i].max()) <= 1e-4 * zmax
+  counts = np.zeros(shape[1], np.int64)
+  for i in range(600):  # uniform at eps = 1: every count within 5 sd of 100
+    action, value = lrn.act(s_t[0], 1.0, seed=9, counter=100 + i)
+    counts[action] += 1
+    assert abs(value - q_ref[0].max()) <= 1e-4 * zmax
+  sd = np.sqrt(600 * (1 / 6) * (5 / 6))
+  print('eps = 1 action counts', counts)
+  assert (np.abs(counts - 100) <= 5 * sd).all()
+
+
+def test_create_refuses_a_support_that_does_not_increase(device):
+  from dqn_mgsc_zoo_amd import _native
+  lib = _native.lib()
+  cfg = _native.DqzLearnerConfig(8, 6, _native.ALGO_DQN, LR, 0.0, ADAM_EPS, 0.0)
+  h = ctypes.c_void_p()
+  for bad, atom in (([-1.0, 0.0, 0.0, 1.0], 2), ([0.0, 1.0, 0.5], 2), ([0.0, float('nan'), 2.0], 1)):
+    sup = torch.tensor(bad, dtype=torch.float32, device=device)
+    assert lib.dqz_c51_create(ctypes.byref(cfg), len(bad), _native.ptr(sup), ctypes.byref(h)) == -1
+    assert lib.dqz_last_error() == b'support must be finite and strictly increasing (atom %d)' % atom
+
+
+# -- the agent -------------------------------------------------------------------
+
+def _agent(seed, optimizer=None, num_atoms=51):
+  from dqn_mgsc_zoo_amd import networks
+  from dqn_mgsc_zoo_amd import parts
+  from dqn_mgsc_zoo_amd import replay as replay_lib
+  from dqn_mgsc_zoo_amd.c51 import agent as agent_lib
+  support = c51_ref.make_support(VMAX, num_atoms)
+  replay = replay_lib.TransitionReplay(1000, replay_lib.Transition(None, None, None, None, None),
+                                       np.random.RandomState(seed))
+  agent = agent_lib.C51(
+      preprocessor=fake_env.FrameStacker(),
+      sample_network_input=np.zeros((84, 84, 4), np.uint8),
+      network=networks.c51_atari_network(6, support), support=support,
+      optimizer=optimizer or _optimizer(),
+      transition_accumulator=replay_lib.TransitionAccumulator(),
+      replay=replay, batch_size=10,
+      exploration_epsilon=parts.LinearSchedule(begin_t=40, decay_steps=100, begin_value=1.0, end_value=0.1),
+      min_replay_capacity_fraction=0.05, learn_period=2, target_network_update_period=4,
+      rng_key=np.array([0, seed], np.uint32))
+  return agent, replay
+
+
+def _run(agent, num_steps, seed=1, episode_len=23):
+  from dqn_mgsc_zoo_amd import parts
+  env = fake_env.FakeAtari(episode_len=episode_len, seed=seed)
+  loop = parts.run_loop(agent, env, max_steps_per_episode=0)
+  for _ in range(num_steps):
+    next(loop)
+
+
+def test_agent_learns_and_syncs_the_target(device):
+  """c51/run_atari_test.py's sizes: replay 1000, batch 10, learn period 2,
+  target period 4."""
+  agent, replay = _agent(0)
+  lrn = agent.learner
+  p0 = lrn.online.clone()
+  assert torch.equal(lrn.online, lrn.target)  # the reference's alias at construction
+  synced = []
+  sync_target = lrn.sync_target
+
+  def spy(*args, **kwargs):
+    sync_target(*args, **kwargs)
+    synced.append((agent._frame_t, lrn.online.clone()))  # pylint: disable=protected-access
+
+  lrn.sync_target = spy
+  _run(agent, 100)
+  assert replay.size >= 50
+  assert int(lrn.count.item()) >= 20  # every second frame once 50 transitions are stored
+  assert not torch.equal(p0, lrn.online) and torch.isfinite(lrn.online).all()
+  assert len(synced) >= 10 and all(t % 4 == 0 for t, _ in synced)
+  assert torch.equal(lrn.target, synced[-1][1]) and not torch.equal(p0, lrn.target)
+  assert np.isfinite(agent.statistics['state_value'])
+  assert set(agent.get_state()) == {'rng_key', 'frame_t', 'opt_state', 'online_params', 'target_params', 'replay'}
+  assert agent.check_learner_health() == 0
+
+
+def test_agent_state_round_trip_and_checkpoint_kinds(device):
+  from dqn_mgsc_zoo_amd import learner as learner_lib
+  from dqn_mgsc_zoo_amd import optim_state
+  a1, r1 = _agent(4)
+  _run(a1, 90, seed=5)
+  state = copy.deepcopy(a1.get_state())
+  inner = optim_state.chained_inner(state['opt_state'])
+  assert isinstance(inner[0], optim_state.ScaleByAdamState) and int(inner[0].count) > 0
+  a2, r2 = _agent(99)
+  a2.set_state(state)  # a checkpoint with an Adam state restores
+  r2._random_state.set_state(r1._random_state.get_state())  # pylint: disable=protected-access
+  assert int(a2.learner.count.item()) == int(a1.learner.count.item())
+  env = fake_env.FakeAtari(episode_len=17, seed=6)
+  steps = [env.reset()]
+  for t in range(20):
+    steps.append(env.step(t % 6) if not steps[-1].last() else env.reset())
+  for ts in steps:
+    if ts.first():
+      a1.reset()
+      a2.reset()
+    assert a1.step(ts) == a2.step(ts)
+  for which in ('online', 'target', 'mu', 'nu', 'count'):
+    assert torch.equal(getattr(a1.learner, which), getattr(a2.learner, which))
+  assert int(a1.learner.count.item()) > int(inner[0].count)  # they learned on the way
+  # a DQN agent's checkpoint (centered RMSProp) is refused by name, clipped or not
+  zeros = a1.learner.params_tree('mu')
+  bad = dict(state, opt_state=optim_state.rmsprop_state(zeros, zeros))
+  with pytest.raises(ValueError, match='centered-RMSProp state'):
+    a2.set_state(bad)
+  a3, _ = _agent(5, optimizer=learner_lib.adam(LR, eps=ADAM_EPS))
+  with pytest.raises(ValueError, match='centered-RMSProp state'):
+    a3.learner.load_opt_state(optim_state.rmsprop_state(zeros, zeros))
+  with pytest.raises(NotImplementedError, match='centered'):
+    _agent(6, optimizer=learner_lib.rmsprop(LR, 0.95, 1e-5, centered=True))
