@@ -349,11 +349,18 @@ struct Conv2BwdArgs {
 // polls the sample's counter, and every dy2 load is an sc1 (L1-bypassing)
 // buffer load.  PUB: dy1 is handed on to the conv1 dW jobs of the same launch
 // (sc1 stores + arrival on sync1).
-template <bool WAIT, bool PUB = false>
-__device__ __forceinline__ void conv2_bwd_dx(const Conv2BwdArgs& a, float* s_win, int b, int ph, int pw, int hh) {
+// PRE: the operands that are not handed off (W2 fragments, relu'(y1)) were
+// issued by the caller (conv2_dx_issue: the chain block of bwd_bc_kernel) and
+// come in *pre; otherwise the job loads them first.
+struct Conv2DxOps {
+  float wr[16];   // wr[4 t + j] = W2[kh(t)][kw(t)][16 hh + n][16 w + 4 j + kq]
+  float4 ym4[2];  // relu'(y1) operands of the epilogue
+};
+
+__device__ __forceinline__ void conv2_dx_issue(const Conv2BwdArgs& a, int b, int ph, int pw, int hh, float (&wr)[16],
+                                               float4 (&ym4)[2]) {
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int n = lane & 15, kq = lane >> 4;
-  float wr[16];  // wr[4 t + j] = W2[kh(t)][kw(t)][16 hh + n][16 w + 4 j + kq]
   {
     const float4* wp =
         reinterpret_cast<const float4*>(a.w2p) + (((((ph * 2 + pw) * 2 + hh) * 4) * 4 + w) * 16 + n) * 4 + kq;
@@ -368,12 +375,45 @@ __device__ __forceinline__ void conv2_bwd_dx(const Conv2BwdArgs& a, float* s_win
   }
   // relu'(y1) operands of the epilogue, loaded early: thread t owns output
   // positions q = t / 4 and q + 64 (< 100), channels 16 hh + 4 (t & 3) .. +3
-  float4 ym4[2];
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int q = min((t >> 2) + 64 * k, 99), ah = q / 10, cw = q % 10;
     ym4[k] = *reinterpret_cast<const float4*>(a.y1 + ((int64_t)b * C1M + (2 * ah + ph) * C1O + 2 * cw + pw) * C1CO +
                                               16 * hh + 4 * (t & 3));
+  }
+}
+
+template <bool WAIT, bool PUB = false, bool PRE = false>
+__device__ __forceinline__ void conv2_bwd_dx(const Conv2BwdArgs& a, float* s_win, int b, int ph, int pw, int hh,
+                                             const Conv2DxOps* pre = nullptr) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int n = lane & 15, kq = lane >> 4;
+  float wr[16];  // wr[4 t + j] = W2[kh(t)][kw(t)][16 hh + n][16 w + 4 j + kq]
+  float4 ym4[2];
+  if constexpr (PRE) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) wr[k] = pre->wr[k];
+    ym4[0] = pre->ym4[0];
+    ym4[1] = pre->ym4[1];
+  } else {
+    // conv2_dx_issue's loads, spelled out: through the call, this grid's code
+    // came out with another register allocation than before the split
+    const float4* wp =
+        reinterpret_cast<const float4*>(a.w2p) + (((((ph * 2 + pw) * 2 + hh) * 4) * 4 + w) * 16 + n) * 4 + kq;
+#pragma unroll
+    for (int tp = 0; tp < 4; ++tp) {
+      const float4 v = wp[tp * 256];
+      wr[4 * tp] = v.x;
+      wr[4 * tp + 1] = v.y;
+      wr[4 * tp + 2] = v.z;
+      wr[4 * tp + 3] = v.w;
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int q = min((t >> 2) + 64 * k, 99), ah = q / 10, cw = q % 10;
+      ym4[k] = *reinterpret_cast<const float4*>(a.y1 + ((int64_t)b * C1M + (2 * ah + ph) * C1O + 2 * cw + pw) * C1CO +
+                                                16 * hh + 4 * (t & 3));
+    }
   }
   const float4* src = reinterpret_cast<const float4*>(a.dy2 + (int64_t)b * (C2M * C2CO));
   constexpr int NW4 = 121 * 16;  // 1936
@@ -836,19 +876,75 @@ DQZ_STEP_KERNEL __launch_bounds__(256) void fc1_dx_kernel(Fc1BwdArgs a) {
   fc1_dx_block(a, smem, blockIdx.x);
 }
 
-// bwd_bc_kernel: the whole backward after fc1 dX in one launch.  Grid, in
-// dispatch order:
+// One block of bwd_bc_kernel's chain grid: job j of sample s carried through
+// the three dX-chain stages in turn, conv3 dX (nq = j & 3, mh = j >> 2) ->
+// conv2 dX (ph = (j & 3) >> 1, pw = j & 1, hh = j >> 2) -> conv1 dW (rb =
+// j >> 1, ch = j & 1): the job bodies and the Handoff protocol of the
+// separate ranges, in a workgroup that is already resident when its hand-off
+// completes.  A stage's operands that are not handed off are issued as soon
+// as the stage before has arrived, so they land under the wait for the
+// sample's other seven jobs: stage 2's W2 fragments and relu'(y1) operands
+// (24 VGPRs) and stage 3's frame ids after stage 1, stage 3's frame pieces (4
+// VGPRs) after stage 2; the slot is read first of all.  The sched_barriers
+// keep the loads in front of the wait (the scheduler otherwise sinks them to
+// their first use, behind it).  Issued earlier still, inside the stage before
+// (after its MFMA loop), they measured slower: DESIGN §4 "Round 7".  The LDS
+// union is reused from stage to stage: a stage's last LDS reads are followed
+// by arrive()'s barrier, and the next stage writes LDS only after its
+// wait()'s barrier.
+__device__ __forceinline__ void bwd_chain_block(const Conv3BwdArgs& c3, const Conv2BwdArgs& c2, const Conv1DwArgs& c1,
+                                                float* smem, int s, int j) {
+  const int ph = (j & 3) >> 1, pw = j & 1, hh = j >> 2, rb = j >> 1, ch = j & 1;
+  const int slot = c1.src.slots[s];
+  DQZ_STAMP(6, 0);
+  conv3_bwd_dx<true>(c3, smem, s, j & 3, j >> 2);
+  DQZ_STAMP(6, 3);
+  DQZ_STAMP(7, 0);
+  Conv2DxOps o2;
+  conv2_dx_issue(c2, s, ph, pw, hh, o2.wr, o2.ym4);
+  const Conv1DwFrames fr = conv1_dw_frame_ids(c1, ch, slot);
+  __builtin_amdgcn_sched_barrier(0);
+  conv2_bwd_dx<true, true, true>(c2, smem, s, ph, pw, hh, &o2);
+  DQZ_STAMP(7, 3);
+  __builtin_amdgcn_s_setprio(2);  // the launch's tail next
+  DQZ_STAMP(8, 0);
+  const uint4 v = conv1_dw_issue(c1, rb, fr);
+  __builtin_amdgcn_sched_barrier(0);
+  conv1_dw_body<true>(c1, smem, v, rb, ch, s);
+}
+
+// bwd_bc_kernel: the whole backward after fc1 dX in one launch.  Hand-offs
+// inside the launch (common.hpp Handoff): dy2 from the 8 conv3 dX jobs of a
+// sample to its 8 conv2 dX and 8 conv2 dW jobs, dy1 from the 8 conv2 dX jobs
+// to its 8 conv1 dW jobs.  Two grids, in dispatch order:
+//
+// CHAIN (legal for at most BWD_CHAIN_MAXB samples and the default for 2 .. BWD_CHAIN_MAXB:
+// learner_impl.hpp bwd_chain_active, dqz_learner_debug_backward):
+//   [chain 8/sample] [fc1 dW 784] [conv3 dW 4/sample] [conv2 dW 8/sample]
+// A chain block carries job j of its sample through conv3 dX, conv2 dX and
+// conv1 dW (bwd_chain_block above), so the dX chain never waits for a
+// dispatch.  Termination: the chain blocks have the lowest indices and
+// workgroups are dispatched in index order.  A chain block waits only on the
+// seven peers of its sample, which lie in the same group of 64 consecutive
+// blocks (xcd_sample_job_at: 8 samples x 8 jobs); every lower group is fully
+// dispatched and its blocks retire without waiting on anything later; and
+// there are at most 8 * 64 = 512 chain blocks (plus the 8 write-back
+// workgroups) against at least 1024 workgroup slots (256 CUs x 4 at this LDS
+// size and waves_per_eu(4, 8)), so a whole group is always resident together
+// whatever else runs.  The conv2 dW blocks wait on dy2 from blocks of lower
+// index, as before.  The bounded spin and the error word (Handoff::wait,
+// dqz_learner_sync_status) stay as the backstop.
+//
+// !CHAIN (larger batches: the MGSC meta batches; one sample):
 //   [conv3 dX 8/sample] [fc1 dW 784] [conv2 dX 8/sample]
 //   [conv3 dW 4/sample] [conv1 dW 8/sample] [conv2 dW 8/sample]
-// Hand-offs inside the launch (common.hpp Handoff): dy2 from
-// the 8 conv3 dX jobs of a sample to its 8 conv2 dX and 8 conv2 dW jobs, dy1
-// from the 8 conv2 dX jobs to its 8 conv1 dW jobs.  Every consumer has a
-// higher block index than its producers and workgroups are dispatched in
-// index order, so every wait terminates.  The first two ranges fill the chip
-// (4 workgroups per CU), so consumers are dispatched as conv3 dX blocks
-// retire instead of spinning from the start.  Sample jobs keep the XCD-aware
-// decode (each range starts at a multiple of 8, so producer and consumer
-// share an L2).
+// Every consumer has a higher block index than its producers and workgroups
+// are dispatched in index order, so every wait terminates.  The first two
+// ranges fill the chip (4 workgroups per CU), so consumers are dispatched as
+// conv3 dX blocks retire instead of spinning from the start.
+//
+// In both, sample jobs keep the XCD-aware decode (each range starts at a
+// multiple of 8, so producer and consumer share an L2).
 // With a PER write-back (wb.tree set, dqz_learner_step_per) the grid gets 8
 // leading workgroups: wave 0 of the first runs per_write_back_wave beside the
 // whole backward (the TD errors are final since the head), the other seven
@@ -860,7 +956,13 @@ DQZ_STEP_KERNEL __launch_bounds__(256) void fc1_dx_kernel(Fc1BwdArgs a) {
 // conv3 dW at 1 as well: +0.3 %; the forward's conv2 / conv3 consumers above
 // their producers: -0.8 %; profiles/r06/prio).
 // alternatives measured: DESIGN §4 "Tried in round 5", "Round 6: what was tried on the step"
-template <bool WB>
+constexpr int BWD_CHAIN_MAXB = 64;  // 8 * ceil8(B) <= 512 chain blocks
+inline int bwd_bc_blocks(int B, bool wb, bool chain) {
+  const int B8 = (B + 7) / 8 * 8;
+  return (wb ? 8 : 0) + 8 * B8 + 4 * (FLAT / 16) + 4 * B8 + 8 * B8 + (chain ? 0 : 16 * B8);
+}
+
+template <bool WB, bool CHAIN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void bwd_bc_kernel(
     Conv3BwdArgs c3, Fc1BwdArgs f1, Conv2BwdArgs c2, Conv1DwArgs c1, PerWbArgs wb) {
   constexpr int kW = C3X_WIN > FC1W_SMEM ? C3X_WIN : FC1W_SMEM;
@@ -884,9 +986,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     const SampleJob sj = xcd_sample_job_at(i, 8, c3.B);
     if (!sj.valid) return;
     __builtin_amdgcn_s_setprio(3);  // the dX chain first (see above)
-    DQZ_STAMP(6, 0);
-    conv3_bwd_dx<true>(c3, smem, sj.s, sj.job & 3, sj.job >> 2);
-    DQZ_STAMP(6, 3);
+    if constexpr (CHAIN) {
+      bwd_chain_block(c3, c2, c1, smem, sj.s, sj.job);
+    } else {
+      DQZ_STAMP(6, 0);
+      conv3_bwd_dx<true>(c3, smem, sj.s, sj.job & 3, sj.job >> 2);
+      DQZ_STAMP(6, 3);
+    }
     return;
   }
   i -= 8 * B8;
@@ -895,16 +1001,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     return;
   }
   i -= NF;
-  if (i < 8 * B8) {
-    const SampleJob sj = xcd_sample_job_at(i, 8, c2.B);
-    if (!sj.valid) return;
-    __builtin_amdgcn_s_setprio(3);  // the dX chain first (see above)
-    DQZ_STAMP(7, 0);
-    conv2_bwd_dx<true, true>(c2, smem, sj.s, (sj.job & 3) >> 1, sj.job & 1, sj.job >> 2);
-    DQZ_STAMP(7, 3);
-    return;
+  if constexpr (!CHAIN) {
+    if (i < 8 * B8) {
+      const SampleJob sj = xcd_sample_job_at(i, 8, c2.B);
+      if (!sj.valid) return;
+      __builtin_amdgcn_s_setprio(3);  // the dX chain first (see above)
+      DQZ_STAMP(7, 0);
+      conv2_bwd_dx<true, true>(c2, smem, sj.s, (sj.job & 3) >> 1, sj.job & 1, sj.job >> 2);
+      DQZ_STAMP(7, 3);
+      return;
+    }
+    i -= 8 * B8;
   }
-  i -= 8 * B8;
   if (i < 4 * B8) {
     const SampleJob sj = xcd_sample_job_at(i, 4, c3.B);
     if (!sj.valid) return;
@@ -914,17 +1022,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     return;
   }
   i -= 4 * B8;
-  // conv1 dW (the launch's tail: it waits for dy1) is dispatched ahead of
-  // conv2 dW (whose dy2 is ready early): 14,003-14,012 -> 14,178-14,198
-  // steps/s; ahead of conv3 dW as well measured the same
-  if (i < 8 * B8) {
-    const SampleJob sj = xcd_sample_job_at(i, 8, c1.B);
-    if (!sj.valid) return;
-    __builtin_amdgcn_s_setprio(2);  // the launch's tail next
-    conv1_dw_half(c1, smem, sj.job >> 1, sj.job & 1, sj.s);
-    return;
+  if constexpr (!CHAIN) {
+    // conv1 dW (the launch's tail: it waits for dy1) is dispatched ahead of
+    // conv2 dW (whose dy2 is ready early): 14,003-14,012 -> 14,178-14,198
+    // steps/s; ahead of conv3 dW as well measured the same
+    if (i < 8 * B8) {
+      const SampleJob sj = xcd_sample_job_at(i, 8, c1.B);
+      if (!sj.valid) return;
+      __builtin_amdgcn_s_setprio(2);  // the launch's tail next
+      conv1_dw_half(c1, smem, sj.job >> 1, sj.job & 1, sj.s);
+      return;
+    }
+    i -= 8 * B8;
   }
-  i -= 8 * B8;
   const SampleJob sj = xcd_sample_job_at(i, 8, c2.B);
   if (!sj.valid) return;
   DQZ_STAMP(13, 0);

@@ -337,23 +337,56 @@ struct Conv1DwArgs {
 constexpr int C1H_TLD = 136;  // bf16 per co row of the dy1 image (272 B: 16-byte lane reads spread over the banks)
 constexpr int C1H_SMEM = (2 * C1_PLANE * 2 + 3 * C1CO * C1H_TLD * 2) / 4 + 16 * C1CO;  // floats
 
-__device__ __forceinline__ void conv1_dw_half(const Conv1DwArgs& a, float* smem, int rb, int ch, int b) {
-  DQZ_STAMP(8, 0);
+// The links of the job's operand chain, slot -> frame ids -> frame pieces, are
+// also functions of their own (conv1_dw_frame_ids, conv1_dw_issue), so the
+// chain block of bwd_bc_kernel can issue each ahead of this stage and run the
+// rest ("wait + run", conv1_dw_body<true>) on the pieces it holds.
+struct Conv1DwFrames {
+  int fa, fb;  // frame ids of channels 2 ch and 2 ch + 1 (-1: zero padding)
+};
+
+__device__ __forceinline__ Conv1DwFrames conv1_dw_frame_ids(const Conv1DwArgs& a, int ch, int slot) {
+  const int32_t* fr = a.src.fidx + (int64_t)slot * 8 + a.which * 4 + 2 * ch;
+  return Conv1DwFrames{fr[0], fr[1]};
+}
+
+// frames of the two channels: 2 x 126 16-byte pieces, one per thread
+__device__ __forceinline__ uint4 conv1_dw_issue(const Conv1DwArgs& a, int rb, const Conv1DwFrames fr) {
+  const int row0 = rb * C1S * C1_ROWS;
+  constexpr int QPC = C1_PLANE / 16;  // 126
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  const int tid = threadIdx.x;
+  const int cl = tid / QPC, pj = tid % QPC;  // threads 0..251: channel cl, piece pj
+  const int f = cl == 0 ? fr.fa : fr.fb;
+  if (tid < 2 * QPC && f >= 0)
+    v = reinterpret_cast<const uint4*>(a.src.frames + (int64_t)f * FB + row0 * FW)[pj];
+  return v;
+}
+
+// PRE: the frame pieces were issued earlier (vpre); otherwise the job loads its
+// own operand chain first, as the separate conv1 dW range does.
+template <bool PRE>
+__device__ __forceinline__ void conv1_dw_body(const Conv1DwArgs& a, float* smem, const uint4 vpre, int rb, int ch,
+                                              int b) {
   uint16_t* s_in = reinterpret_cast<uint16_t*>(smem);  // 2 planes x 2016 bf16
   uint16_t* s_dt = s_in + 2 * C1_PLANE;                 // [3][32][C1H_TLD] bf16
   float* s_bp = smem + (2 * C1_PLANE + 3 * C1CO * C1H_TLD) / 2;  // [16][32] per-chunk dy1 sums (db)
   // frames of the two channels: slot -> fidx -> 2 x 126 16-byte pieces
   const int row0 = rb * C1S * C1_ROWS;
   constexpr int QPC = C1_PLANE / 16;  // 126
-  const int slot = a.src.slots[b];
-  const int32_t* fr = a.src.fidx + (int64_t)slot * 8 + a.which * 4 + 2 * ch;
-  const int fa = fr[0], fb = fr[1];
   uint4 v = make_uint4(0u, 0u, 0u, 0u);
   const int tid = threadIdx.x;
   const int cl = tid / QPC, pj = tid % QPC;  // threads 0..251: channel cl, piece pj
-  const int f = cl == 0 ? fa : fb;
-  if (tid < 2 * QPC && f >= 0)
-    v = reinterpret_cast<const uint4*>(a.src.frames + (int64_t)f * FB + row0 * FW)[pj];
+  if constexpr (PRE) {
+    v = vpre;
+  } else {
+    const int slot = a.src.slots[b];
+    const int32_t* fr = a.src.fidx + (int64_t)slot * 8 + a.which * 4 + 2 * ch;
+    const int fa = fr[0], fb = fr[1];
+    const int f = cl == 0 ? fa : fb;
+    if (tid < 2 * QPC && f >= 0)
+      v = reinterpret_cast<const uint4*>(a.src.frames + (int64_t)f * FB + row0 * FW)[pj];
+  }
   a.sync1.wait(b);
   const float* dyb = a.dy1 + ((int64_t)b * C1M + rb * C1_POS) * C1CO;
   const int co = tid & 31, c0 = tid >> 5;  // this thread: chunks c0 and c0 + 8 of channel co
@@ -433,6 +466,11 @@ __device__ __forceinline__ void conv1_dw_half(const Conv1DwArgs& a, float* smem,
           f32x4{div255(acc[4 * q]), div255(acc[4 * q + 1]), div255(acc[4 * q + 2]), div255(acc[4 * q + 3])};
   }
   DQZ_STAMP(8, 3);
+}
+
+__device__ __forceinline__ void conv1_dw_half(const Conv1DwArgs& a, float* smem, int rb, int ch, int b) {
+  DQZ_STAMP(8, 0);
+  conv1_dw_body<false>(a, smem, make_uint4(0u, 0u, 0u, 0u), rb, ch, b);
 }
 
 }  // namespace dqz

@@ -45,6 +45,7 @@ struct dqz_learner {
   int32_t* ga;
   int32_t* sync;  // hand-off words and the error word: read them through sync_of / handoff (below)
   unsigned spin_max = 1u << 24;  // hand-off polls before a wait gives up
+  int bwd_chain = -1;            // bwd_bc_kernel's grid: -1 the default, 0 / 1 forced (dqz_learner_debug_backward)
   void* block;
 };
 
@@ -58,6 +59,15 @@ inline Handoff handoff(const dqz_learner* L, const HandoffWords& w) {
   Handoff h{L->sync + w.cnt, L->sync + w.ack, L->sync + sync_of(L).err(), w.need, w.consumers};
   if (w.learner_spin) h.spin_max = L->spin_max;  // dqz_learner_debug_stall shortens the backward's waits only
   return h;
+}
+
+// Whether the learner's next backward launch runs bwd_bc_kernel's chain grid (bwd.hpp): legal up to
+// BWD_CHAIN_MAXB samples (the termination argument above the kernel), and there the default, except for the
+// one-sample learner: nothing queues for a slot on an empty chip, and the MGSC meta-update's B = 1 passes measured
+// 1 % slower chained (DESIGN §4 "Round 7").
+inline bool bwd_chain_active(const dqz_learner* L) {
+  if (L->cfg.batch > BWD_CHAIN_MAXB) return false;
+  return L->bwd_chain < 0 ? L->cfg.batch > 1 : L->bwd_chain != 0;
 }
 
 inline int check_store(const dqz_store* S) {

@@ -346,7 +346,6 @@ int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, c
   c1dw.part = L->p1;
   c1dw.sync1 = handoff(L, sync_of(L).dy1());
   c2b.sync1 = c1dw.sync1;
-  const int B8 = (B + 7) / 8 * 8;
   PerWbArgs wbk{};
   const bool wb = r.wb != nullptr;
   if (wb) {
@@ -354,9 +353,11 @@ int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, c
     wbk.td = L->td;
     wbk.n = B;
   }
-  const int grid = (wb ? 8 : 0) + 8 * B8 + 4 * (FLAT / 16) + 8 * B8 + 4 * B8 + 8 * B8 + 8 * B8;
-  DQZ_PHASE(6, if (wb) hipLaunchKernelGGL(bwd_bc_kernel<true>, dim3(grid), dim3(256), 0, st, c3b, fb, c2b, c1dw, wbk);
-            else hipLaunchKernelGGL(bwd_bc_kernel<false>, dim3(grid), dim3(256), 0, st, c3b, fb, c2b, c1dw, wbk);
+  const bool chain = bwd_chain_active(L);
+  const dim3 grid(bwd_bc_blocks(B, wb, chain));
+  auto* const bwd = wb ? (chain ? bwd_bc_kernel<true, true> : bwd_bc_kernel<true, false>)
+                       : (chain ? bwd_bc_kernel<false, true> : bwd_bc_kernel<false, false>);
+  DQZ_PHASE(6, hipLaunchKernelGGL(bwd, grid, dim3(256), 0, st, c3b, fb, c2b, c1dw, wbk);
             DQZ_HIP(hipGetLastError()));
   if (pe.on() && !r.c51) pe.ms[7] = pe.ms[8] = 0.f;
 
@@ -472,6 +473,14 @@ int dqz_learner_debug_stall(dqz_learner* L, int sample, unsigned spin_max) {
     DQZ_HIP(hipDeviceSynchronize());
     DQZ_HIP(hipMemcpy(L->sync + at.dy2().cnt + at.word(sample), &poison, sizeof(poison), hipMemcpyHostToDevice));
   }
+  return DQZ_OK;
+}
+
+int dqz_learner_debug_backward(dqz_learner* L, int chain, int* active) {
+  if (!L) return fail(DQZ_ERR_INVALID, "null learner");
+  if (chain < -1 || chain > 1) return fail(DQZ_ERR_INVALID, "chain must be -1, 0 or 1");
+  L->bwd_chain = chain;
+  if (active) *active = bwd_chain_active(L) ? 1 : 0;
   return DQZ_OK;
 }
 

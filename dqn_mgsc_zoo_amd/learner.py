@@ -379,6 +379,17 @@ class Learner:
     counter (sample >= 0) and cap the bounded spin at `spin_max` polls."""
     _native.check(_native.lib().dqz_learner_debug_stall(self._h, int(sample), int(spin_max)))
 
+  def debug_backward(self, chain=-1):
+    """Test hook (dqz_learner_debug_backward): the backward launch's grid from
+    the next step on: 1 the chain grid where it is legal (batch <= 64), 0
+    the separate block ranges, -1 the default (the chain for 2 <= batch <=
+    64).  Returns what the next step
+    will use (1 or 0); both compute the same bits."""
+    active = ctypes.c_int(-1)
+    _native.check(_native.lib().dqz_learner_debug_backward(
+        self._h, int(chain), ctypes.byref(active)))
+    return active.value
+
   def fetch_activations(self, z=0, backward=False, stream=None):
     """Diagnostic (dqz_learner_debug_activations): the intermediates of the
     most recent step / gradient call as a dict of fresh device tensors.

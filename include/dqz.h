@@ -237,6 +237,17 @@ int dqz_learner_sync_status(dqz_learner* learner, int* status);
  * exercised.  Synchronises the device. */
 int dqz_learner_debug_stall(dqz_learner* learner, int sample, unsigned spin_max);
 
+/* Diagnostic (tests, A/B timing): which grid the backward launch
+ * (bwd_bc_kernel) uses from the next enqueued step on.  chain = 1 forces the
+ * chain grid (one resident workgroup carries a job through conv3 dX, conv2
+ * dX and conv1 dW) where it is legal (batch <= 64), 0 forces the grid of
+ * separate block ranges, -1 restores the default (the chain grid for
+ * 2 <= batch <= 64).  Both compute the same
+ * bits.  *active (may be NULL) returns what the next step will use: 1 the
+ * chain grid, 0 the separate ranges.  A captured graph keeps the grid it was
+ * captured with. */
+int dqz_learner_debug_backward(dqz_learner* learner, int chain, int* active);
+
 /* Diagnostic (tests): device-to-device copies of the intermediates the
  * learner's scratch holds after its most recent learner step, gradient call
  * or forward (any output may be NULL; no kernel is launched; the copies are

@@ -1,7 +1,11 @@
 """Per-kernel timeline of one learner step from in-kernel s_memrealtime stamps.
 
-usage (GPU box): [ALGO=dqn|double|per|mgsc] python tools/trace_step.py
+usage (GPU box): [ALGO=dqn|double|per|mgsc] [CHAIN=0|1] python tools/trace_step.py
 (builds libdqz_trace.so first, unless DQZ_TRACE_PREBUILT=1)
+CHAIN (ALGO=dqn) forces the backward launch's grid (Learner.debug_backward): with
+the chain grid the conv3_dx / conv2_dx / conv1_dw rows are the three stages of the
+same workgroups (conv2_dx s0-s1 is its wait for dy2 plus the window staging,
+conv1_dw s0-s1 its wait for dy1 plus the dy1 staging).
 Prints, per kernel in launch order: first-block start relative to the previous
 kernel's last-block end (the boundary), kernel span, median block lifetime and
 the median of the named intervals between stamps (10 ns ticks -> us).
@@ -37,6 +41,8 @@ if ALGO == 'dqn':
   net = networks.dqn_atari_network(6)
   lrn = learner_lib.Learner(net, BATCH, algo='dqn', device=dev)
   lrn.set_params(net.init(0))
+  if os.environ.get('CHAIN'):
+    print('backward grid: %s' % ('chain' if lrn.debug_backward(int(os.environ['CHAIN'])) else 'block ranges'))
   store = synthetic.fill_episodic(cap, 6, seed=0, device=dev)
   slots = torch.zeros((BATCH,), dtype=torch.int32, device=dev)
   counter = torch.zeros((1,), dtype=torch.int64, device=dev)
