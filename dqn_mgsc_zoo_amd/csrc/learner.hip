@@ -110,7 +110,7 @@ int dqz_gather_stacks(const dqz_store* S, const int32_t* slots, int n, int which
   if (int rc = check_store(S)) return rc;
   if (!slots || !out) return fail(DQZ_ERR_INVALID, "null argument");
   if (n < 0) return fail(DQZ_ERR_INVALID, "n must be >= 0");
-  if (which != 0 && which != 1) return fail(DQZ_ERR_INVALID, "which must be 0 (s_tm1) or 1 (s_t)");
+  if (int rc = check_which(which)) return rc;
   if (n == 0) return DQZ_OK;
   const int64_t total = (int64_t)n * FB;
   hipLaunchKernelGGL(gather_stacks_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
@@ -619,29 +619,30 @@ int dqz_per_sample(const double* tree, int64_t cap, int64_t live_base, int64_t s
   return DQZ_OK;
 }
 
-// dqz_learner_step_per_draw, or with gout the same step in gradient mode
-// (dqz_learner_step_opt_per_draw)
-static int per_draw_step(dqz_learner* L, const dqz_params* P, const dqz_store* S, const dqz_per_draw* d, float* gout,
-                         void* stream) {
+// The fused prioritized step's draw and write-back (dqz_learner_step_per_draw, dqz_learner_step_opt_per_draw):
+// d's checks, then *a and *wb, the request's pd and wb.
+static int per_draw_request(const dqz_learner* L, const dqz_per_draw* d, PerSampleArgs* a, PerWbArgs* wb) {
   if (!L || !d || !d->tree || !d->out_indices || !d->out_slots || !d->out_probs || !d->max_seen_dev)
     return fail(DQZ_ERR_INVALID, "null argument");
   if (L->cfg.algo != DQZ_ALGO_PER) return fail(DQZ_ERR_INVALID, "the learner is not a PER learner");
-  PerSampleArgs a{.tree = d->tree, .cap = d->cap, .live_base = d->live_base, .size = d->size,
-                  .capacity = d->capacity, .n = L->cfg.batch, .usp = d->uniform_sample_probability,
-                  .beta = d->importance_sampling_exponent, .normalize = d->normalize_weights, .seed = d->seed,
-                  .counter = d->counter_dev, .inj_uniform = d->injected_uniform, .inj_u = d->injected_u,
-                  .index_to_slot = d->index_to_slot, .out_indices = d->out_indices, .out_slots = d->out_slots,
-                  .out_weights = d->out_weights, .out_probs = d->out_probs};
-  if (int rc = per_draw_args(&a)) return rc;
-  PerWbArgs wb;
-  if (!per_wb_args(L, d->tree, d->cap, d->out_indices, d->alpha, d->max_seen_dev, &wb))
+  *a = PerSampleArgs{.tree = d->tree, .cap = d->cap, .live_base = d->live_base, .size = d->size,
+                     .capacity = d->capacity, .n = L->cfg.batch, .usp = d->uniform_sample_probability,
+                     .beta = d->importance_sampling_exponent, .normalize = d->normalize_weights, .seed = d->seed,
+                     .counter = d->counter_dev, .inj_uniform = d->injected_uniform, .inj_u = d->injected_u,
+                     .index_to_slot = d->index_to_slot, .out_indices = d->out_indices, .out_slots = d->out_slots,
+                     .out_weights = d->out_weights, .out_probs = d->out_probs};
+  if (int rc = per_draw_args(a)) return rc;
+  if (!per_wb_args(L, d->tree, d->cap, d->out_indices, d->alpha, d->max_seen_dev, wb))
     return fail(DQZ_ERR_INVALID, "the fused PER step takes batch <= 64 and cap <= 2^%d", PWB_LEVELS);
-  return step_impl(L, P, S, {.pd = &a, .gout = gout, .wb = &wb}, stream);
+  return DQZ_OK;
 }
 
 int dqz_learner_step_per_draw(dqz_learner* L, const dqz_params* P, const dqz_store* S, const dqz_per_draw* d,
                               void* stream) {
-  return per_draw_step(L, P, S, d, nullptr, stream);
+  PerSampleArgs a;
+  PerWbArgs wb;
+  if (int rc = per_draw_request(L, d, &a, &wb)) return rc;
+  return step_impl(L, P, S, {.pd = &a, .wb = &wb}, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -768,42 +769,58 @@ int dqz_optimizer_outputs(dqz_optimizer* o, float* gnorm, void* stream) {
   return DQZ_OK;
 }
 
-// what a step in gradient mode followed by dqz_optimizer_apply needs checked
-// before anything is enqueued
-static int check_step_opt(const dqz_learner* L, const dqz_params* P, const dqz_optimizer* o, const int32_t* count) {
-  if (!L || !P || !o) return fail(DQZ_ERR_INVALID, "null argument");
+// What a step in gradient mode followed by dqz_optimizer_apply needs checked before anything is enqueued; the
+// entry has refused a null handle of its own, and L is not read before the layout is compared.
+// num_atoms: 0 for the scalar head, N for the categorical one, whose optimizers have no shared bias
+// (dqz_c51_optimizer_create), as its learner has none.
+static int check_step_apply(const dqz_learner* L, const dqz_params* P, const dqz_optimizer* o, const int32_t* count,
+                            int num_atoms) {
+  if (!P || !o) return fail(DQZ_ERR_INVALID, "null argument");
   if (!P->online || !P->nu) return fail(DQZ_ERR_INVALID, "null optimizer state");
   if (o->cfg.kind == DQZ_OPT_ADAM && (!P->mu || !count)) return fail(DQZ_ERR_INVALID, "Adam needs mu and count");
   if ((reinterpret_cast<uintptr_t>(P->online) | reinterpret_cast<uintptr_t>(P->nu) |
        reinterpret_cast<uintptr_t>(P->mu)) % 16)
     return fail(DQZ_ERR_INVALID, "parameters and moments must be 16-byte aligned");
-  if (o->cfg.num_actions != L->cfg.num_actions || (o->cfg.shared_bias != 0) != (L->shared_bias != 0) || o->num_atoms)
+  if (!L || o->cfg.num_actions != L->cfg.num_actions || (o->cfg.shared_bias != 0) != (L->shared_bias != 0) ||
+      o->num_atoms != num_atoms)
     return fail(DQZ_ERR_INVALID, "the optimizer was created for another parameter layout");
   return DQZ_OK;
 }
 
+// The request's step in gradient mode into the optimizer's own buffer, then the optimizer on it.  An entry whose
+// request has a draw to build calls check_step_apply ahead of that, so a call is refused for its optimizer first.
+static int step_then_apply(dqz_learner* L, const dqz_params* P, const dqz_store* S, StepRequest r, dqz_optimizer* o,
+                           int32_t* count, int num_atoms, void* stream) {
+  if (int rc = check_step_apply(L, P, o, count, num_atoms)) return rc;
+  r.gout = o->grad;
+  if (int rc = step_impl(L, P, S, r, stream)) return rc;
+  return dqz_optimizer_apply(o, P->online, o->grad, P->mu, P->nu, count, stream);
+}
+
 int dqz_learner_step_opt(dqz_learner* L, const dqz_params* P, const dqz_store* S, const int32_t* slots,
                          const float* is_weights, dqz_optimizer* o, int32_t* count, void* stream) {
-  if (int rc = check_step_opt(L, P, o, count)) return rc;
-  if (int rc = step_impl(L, P, S, {.slots = slots, .is_weights = is_weights, .gout = o->grad}, stream)) return rc;
-  return dqz_optimizer_apply(o, P->online, o->grad, P->mu, P->nu, count, stream);
+  if (!L) return fail(DQZ_ERR_INVALID, "null argument");
+  return step_then_apply(L, P, S, {.slots = slots, .is_weights = is_weights}, o, count, 0, stream);
 }
 
 int dqz_learner_step_opt_uniform(dqz_learner* L, const dqz_params* P, const dqz_store* S, int64_t base, int64_t size,
                                  int64_t capacity, uint64_t seed, uint64_t* counter_dev, int32_t* slots_out,
                                  dqz_optimizer* o, int32_t* count, void* stream) {
-  if (int rc = check_step_opt(L, P, o, count)) return rc;
+  if (!L) return fail(DQZ_ERR_INVALID, "null argument");
+  if (int rc = check_step_apply(L, P, o, count, 0)) return rc;
   UniformDraw d;
   if (int rc = uniform_draw_args(L, base, size, capacity, seed, counter_dev, slots_out, &d)) return rc;
-  if (int rc = step_impl(L, P, S, {.draw = &d, .gout = o->grad}, stream)) return rc;
-  return dqz_optimizer_apply(o, P->online, o->grad, P->mu, P->nu, count, stream);
+  return step_then_apply(L, P, S, {.draw = &d}, o, count, 0, stream);
 }
 
 int dqz_learner_step_opt_per_draw(dqz_learner* L, const dqz_params* P, const dqz_store* S, const dqz_per_draw* d,
                                   dqz_optimizer* o, int32_t* count, void* stream) {
-  if (int rc = check_step_opt(L, P, o, count)) return rc;
-  if (int rc = per_draw_step(L, P, S, d, o->grad, stream)) return rc;
-  return dqz_optimizer_apply(o, P->online, o->grad, P->mu, P->nu, count, stream);
+  if (!L) return fail(DQZ_ERR_INVALID, "null argument");
+  if (int rc = check_step_apply(L, P, o, count, 0)) return rc;
+  PerSampleArgs a;
+  PerWbArgs wb;
+  if (int rc = per_draw_request(L, d, &a, &wb)) return rc;
+  return step_then_apply(L, P, S, {.pd = &a, .wb = &wb}, o, count, 0, stream);
 }
 
 int dqz_per_add(double* tree, int64_t cap, int32_t remove_index, int32_t add_index, double priority,
@@ -863,6 +880,7 @@ struct dqz_c51 {
   C51Head head;  // support and outputs, carved from block
   void* block;
 };
+static dqz_learner* learner_of(dqz_c51* C) { return C ? C->L : nullptr; }  // null: the shared checks refuse it
 
 static int c51_check_shape(int A, int N) {
   if (A < 1 || A > MAXA) return fail(DQZ_ERR_INVALID, "num_actions must be in [1, %d]", MAXA);
@@ -942,7 +960,7 @@ int dqz::c51_launch(C51Launch which, dqz_learner* L, const dqz_params* P, const 
 
 // q_values of n states through one copy: the torso, the logits, the head in forward mode (actor: with a draw)
 static int c51_forward_q(dqz_c51* C, const float* params, const Conv1Src& src, int which, int n, float* q_out,
-                         dqz_action* act_out, double eps, uint64_t seed, uint64_t counter, hipStream_t st) {
+                         const ActorDraw* act, hipStream_t st) {
   dqz_learner* L = C->L;
   if (int rc = forward_torso(L, params, src, which, n, st)) return rc;
   const NetZ nz{{params, params, params}, {which, which, which}};
@@ -956,24 +974,14 @@ static int c51_forward_q(dqz_c51* C, const float* params, const Conv1Src& src, i
   h.N = C->N;
   h.fwd_only = 1;
   h.qv = q_out;
-  h.act_out = act_out;
-  h.eps = eps;
-  h.act_seed = seed;
-  h.act_ctr = counter;
+  if (act) {
+    h.act_out = act->out;
+    h.eps = act->eps;
+    h.act_seed = act->seed;
+    h.act_ctr = act->counter;
+  }
   hipLaunchKernelGGL(c51_head_kernel, dim3(n), dim3(HID), 0, st, h);
   DQZ_HIP(hipGetLastError());
-  return DQZ_OK;
-}
-
-static int c51_check_step(const dqz_c51* C, const dqz_params* P, const dqz_optimizer* o, const int32_t* count) {
-  if (!C || !P || !o) return fail(DQZ_ERR_INVALID, "null argument");
-  if (!P->online || !P->nu) return fail(DQZ_ERR_INVALID, "null optimizer state");
-  if (o->cfg.kind == DQZ_OPT_ADAM && (!P->mu || !count)) return fail(DQZ_ERR_INVALID, "Adam needs mu and count");
-  if ((reinterpret_cast<uintptr_t>(P->online) | reinterpret_cast<uintptr_t>(P->nu) |
-       reinterpret_cast<uintptr_t>(P->mu)) % 16)
-    return fail(DQZ_ERR_INVALID, "parameters and moments must be 16-byte aligned");
-  if (o->cfg.num_actions != C->A || o->num_atoms != C->N)
-    return fail(DQZ_ERR_INVALID, "the optimizer was created for another parameter layout");
   return DQZ_OK;
 }
 
@@ -1055,9 +1063,8 @@ int dqz_c51_learner(dqz_c51* C, dqz_learner** out) {
 
 int dqz_c51_step(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, dqz_optimizer* o,
                  int32_t* count, void* stream) {
-  if (int rc = c51_check_step(C, P, o, count)) return rc;
-  if (int rc = step_impl(C->L, P, S, {.slots = slots, .gout = o->grad, .c51 = &C->head}, stream)) return rc;
-  return dqz_optimizer_apply(o, P->online, o->grad, P->mu, P->nu, count, stream);
+  if (!C) return fail(DQZ_ERR_INVALID, "null argument");
+  return step_then_apply(C->L, P, S, {.slots = slots, .c51 = &C->head}, o, count, C->N, stream);
 }
 
 int dqz_c51_grad(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
@@ -1071,15 +1078,7 @@ int dqz_c51_profile(dqz_c51* C, const dqz_params* P, const dqz_store* S, const i
                     int iters, float* phase_ms, void* stream) {
   if (!C) return fail(DQZ_ERR_INVALID, "null argument");
   if (!grad_out) return fail(DQZ_ERR_INVALID, "null grad_out");
-  if (!phase_ms || iters < 1) return fail(DQZ_ERR_INVALID, "phase_ms must be non-null and iters >= 1");
-  for (int i = 0; i < DQZ_NUM_PHASES; ++i) phase_ms[i] = 0.f;
-  PhaseEvents pe{nullptr, nullptr, iters, phase_ms};
-  DQZ_HIP(hipEventCreate(&pe.e0));
-  DQZ_HIP(hipEventCreate(&pe.e1));
-  const int rc = step_impl(C->L, P, S, {.slots = slots, .gout = grad_out, .pe = pe, .c51 = &C->head}, stream);
-  (void)hipEventDestroy(pe.e0);
-  (void)hipEventDestroy(pe.e1);
-  return rc;
+  return profile_step(C->L, P, S, {.slots = slots, .gout = grad_out, .c51 = &C->head}, iters, phase_ms, stream);
 }
 
 int dqz_c51_outputs(dqz_c51* C, float* logits_a, float* q_values, float* loss_b, float* loss, int32_t* a_star,
@@ -1109,35 +1108,25 @@ int dqz_c51_debug(dqz_c51* C, float* logits, float* dlogits, void* stream) {
 }
 
 int dqz_c51_forward(dqz_c51* C, const float* params, const uint8_t* states, int n, float* q_out, void* stream) {
-  if (!C || !params || !states || !q_out) return fail(DQZ_ERR_INVALID, "null argument");
-  if (n < 1 || n > C->L->cfg.batch) return fail(DQZ_ERR_INVALID, "n must be in [1, %d]", C->L->cfg.batch);
-  if (reinterpret_cast<uintptr_t>(states) % 16) return fail(DQZ_ERR_INVALID, "states must be 16-byte aligned");
-  Conv1Src src{nullptr, nullptr, nullptr, states, 0, UniformDraw{}};
-  return c51_forward_q(C, params, src, 0, n, q_out, nullptr, 0.0, 0, 0, (hipStream_t)stream);
+  Conv1Src src;
+  if (int rc = forward_src(learner_of(C), params, n, {.states = states, .q_out = q_out}, &src)) return rc;
+  return c51_forward_q(C, params, src, 0, n, q_out, nullptr, (hipStream_t)stream);
 }
 
 int dqz_c51_forward_slots(dqz_c51* C, const float* params, const dqz_store* S, const int32_t* slots, int n, int which,
                           float* q_out, void* stream) {
-  if (!C || !params || !slots || !q_out) return fail(DQZ_ERR_INVALID, "null argument");
-  if (int rc = check_store(S)) return rc;
-  if (n < 1 || n > C->L->cfg.batch) return fail(DQZ_ERR_INVALID, "n must be in [1, %d]", C->L->cfg.batch);
-  if (which != 0 && which != 1) return fail(DQZ_ERR_INVALID, "which must be 0 (s_tm1) or 1 (s_t)");
-  Conv1Src src{S->frames, S->fidx, slots, nullptr, 0, UniformDraw{}};
-  return c51_forward_q(C, params, src, which, n, q_out, nullptr, 0.0, 0, 0, (hipStream_t)stream);
+  Conv1Src src;
+  const ForwardInput in{.from_store = true, .store = S, .slots = slots, .which = which, .q_out = q_out};
+  if (int rc = forward_src(learner_of(C), params, n, in, &src)) return rc;
+  return c51_forward_q(C, params, src, which, n, q_out, nullptr, (hipStream_t)stream);
 }
 
 int dqz_c51_act(dqz_c51* C, const float* params, const uint8_t* states, int n, double epsilon, uint64_t seed,
                 uint64_t counter, dqz_action* out, void* stream) {
-  if (!C || !params || !states || !out) return fail(DQZ_ERR_INVALID, "null argument");
-  if (n < 1 || n > C->L->cfg.batch) return fail(DQZ_ERR_INVALID, "n must be in [1, %d]", C->L->cfg.batch);
-  if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(DQZ_ERR_INVALID, "epsilon must be in [0, 1]");
-  const void *dstates = nullptr, *dout = nullptr;
-  if (int rc = device_view(states, &dstates, "states")) return rc;
-  if (int rc = device_view(out, &dout, "out")) return rc;
-  if (reinterpret_cast<uintptr_t>(dstates) % 16) return fail(DQZ_ERR_INVALID, "states must be 16-byte aligned");
-  Conv1Src src{nullptr, nullptr, nullptr, static_cast<const uint8_t*>(dstates), 0, UniformDraw{}};
-  return c51_forward_q(C, params, src, 0, n, C->head.qv, static_cast<dqz_action*>(const_cast<void*>(dout)), epsilon,
-                       seed, counter, (hipStream_t)stream);
+  ActorDraw act{epsilon, seed, counter, out};
+  Conv1Src src;
+  if (int rc = forward_src(learner_of(C), params, n, {.states = states, .act = &act}, &src)) return rc;
+  return c51_forward_q(C, params, src, 0, n, C->head.qv, &act, (hipStream_t)stream);
 }
 
 int dqz_c51_debug_check(int batch, unsigned request) {

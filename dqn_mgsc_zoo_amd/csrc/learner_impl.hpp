@@ -2,7 +2,8 @@
 // units (common.hpp, "Two translation units, two code objects"): the learner
 // handle, its parameter layout and hand-off words (layout.hpp), argument
 // checks and the builders of the fused draws' kernel arguments, the forward's
-// argument builder, and the learner step's request (StepRequest) and entry
+// argument builder, the front half of both heads' forward and actor entries
+// (forward_src), and the learner step's request (StepRequest) and entry
 // (step_impl; its two halves are learner_step.hip's) that the MGSC meta-update and the
 // fused samplers in learner.hip call.
 #pragma once
@@ -99,6 +100,57 @@ inline int device_view(const void* p, const void** out, const char* what) {
   } else {
     return fail(DQZ_ERR_INVALID, "%s must be device memory or pinned host memory", what);
   }
+  return DQZ_OK;
+}
+
+inline int check_which(int which) {
+  if (which != 0 && which != 1) return fail(DQZ_ERR_INVALID, "which must be 0 (s_tm1) or 1 (s_t)");
+  return DQZ_OK;
+}
+
+// The actor's eps-greedy draw in a forward's head (dqz_act, dqz_c51_act): draw `counter` of Philox stream `seed`.
+struct ActorDraw {
+  double eps;
+  uint64_t seed, counter;
+  dqz_action* out;  // [n]
+};
+
+// The front half of both heads' forward and actor entries (dqz_forward, dqz_forward_slots, dqz_act and their
+// dqz_c51_* twins): every argument check, in the order the entries have always refused, then conv1's source.  The
+// n inputs are `states` [n][84][84][4] or, with from_store, stack `which` of `store`'s `slots` [n].  The result
+// goes to q_out, or with `act` (the actor's call) to act->out; the actor's states and act->out may be pinned host
+// memory and are replaced by their device views.
+struct ForwardInput {
+  const uint8_t* states;
+  bool from_store;
+  const dqz_store* store;
+  const int32_t* slots;
+  int which;
+  const float* q_out;
+  ActorDraw* act;
+};
+inline int forward_src(const dqz_learner* L, const float* params, int n, ForwardInput in, Conv1Src* src) {
+  if (!L || !params || !(in.from_store ? (const void*)in.slots : in.states) ||
+      !(in.act ? (const void*)in.act->out : in.q_out))
+    return fail(DQZ_ERR_INVALID, "null argument");
+  if (in.from_store)
+    if (int rc = check_store(in.store)) return rc;
+  if (n < 1 || n > L->cfg.batch) return fail(DQZ_ERR_INVALID, "n must be in [1, %d]", L->cfg.batch);
+  if (in.from_store) {
+    if (int rc = check_which(in.which)) return rc;
+    *src = Conv1Src{in.store->frames, in.store->fidx, in.slots, nullptr, 0, UniformDraw{}};
+    return DQZ_OK;
+  }
+  if (ActorDraw* a = in.act) {
+    if (!(a->eps >= 0.0 && a->eps <= 1.0)) return fail(DQZ_ERR_INVALID, "epsilon must be in [0, 1]");
+    const void *dstates = nullptr, *dout = nullptr;
+    if (int rc = device_view(in.states, &dstates, "states")) return rc;
+    if (int rc = device_view(a->out, &dout, "out")) return rc;
+    in.states = static_cast<const uint8_t*>(dstates);
+    a->out = static_cast<dqz_action*>(const_cast<void*>(dout));
+  }
+  if (reinterpret_cast<uintptr_t>(in.states) % 16) return fail(DQZ_ERR_INVALID, "states must be 16-byte aligned");
+  *src = Conv1Src{nullptr, nullptr, nullptr, in.states, 0, UniformDraw{}};
   return DQZ_OK;
 }
 
@@ -237,6 +289,20 @@ int step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, const 
 inline int step_impl(dqz_learner* L, const dqz_params* P, const dqz_store* S, const StepRequest& r, void* stream) {
   if (int rc = check_step(L, P, S, r)) return rc;
   return step_enqueue(L, P, S, r, stream);
+}
+
+// dqz_learner_profile / dqz_c51_profile: the request's step with every phase timed into phase_ms (PhaseEvents).
+inline int profile_step(dqz_learner* L, const dqz_params* P, const dqz_store* S, StepRequest r, int iters,
+                        float* phase_ms, void* stream) {
+  if (!phase_ms || iters < 1) return fail(DQZ_ERR_INVALID, "phase_ms must be non-null and iters >= 1");
+  for (int i = 0; i < DQZ_NUM_PHASES; ++i) phase_ms[i] = 0.f;
+  r.pe = PhaseEvents{nullptr, nullptr, iters, phase_ms};
+  DQZ_HIP(hipEventCreate(&r.pe.e0));
+  DQZ_HIP(hipEventCreate(&r.pe.e1));
+  const int rc = step_impl(L, P, S, r, stream);
+  (void)hipEventDestroy(r.pe.e0);
+  (void)hipEventDestroy(r.pe.e1);
+  return rc;
 }
 
 }  // namespace dqz

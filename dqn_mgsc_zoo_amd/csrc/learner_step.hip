@@ -436,15 +436,7 @@ int dqz_learner_grad(dqz_learner* L, const dqz_params* P, const dqz_store* S, co
 
 int dqz_learner_profile(dqz_learner* L, const dqz_params* P, const dqz_store* S, const int32_t* slots,
                         const float* is_weights, int iters, float* phase_ms, void* stream) {
-  if (!phase_ms || iters < 1) return fail(DQZ_ERR_INVALID, "phase_ms must be non-null and iters >= 1");
-  for (int i = 0; i < DQZ_NUM_PHASES; ++i) phase_ms[i] = 0.f;
-  PhaseEvents pe{nullptr, nullptr, iters, phase_ms};
-  DQZ_HIP(hipEventCreate(&pe.e0));
-  DQZ_HIP(hipEventCreate(&pe.e1));
-  const int rc = step_impl(L, P, S, {.slots = slots, .is_weights = is_weights, .pe = pe}, stream);
-  (void)hipEventDestroy(pe.e0);
-  (void)hipEventDestroy(pe.e1);
-  return rc;
+  return profile_step(L, P, S, {.slots = slots, .is_weights = is_weights}, iters, phase_ms, stream);
 }
 
 int dqz_learner_sync_status(dqz_learner* L, int* status) {
@@ -494,58 +486,44 @@ int dqz_learner_outputs(dqz_learner* L, float* q_tm1, float* td, float* loss, vo
   return DQZ_OK;
 }
 
+// q_values of n states through one copy: the torso, then the head in forward mode (the actor's: with its draw)
 static int forward_q(dqz_learner* L, const float* params, const Conv1Src& src, int which, int n, float* q_out,
-                     hipStream_t st) {
-  const NetZ nz{{params, params, params}, {which, which, which}};
-  if (int rc = forward_impl(L, nz, 1, n, src, st, PhaseEvents{})) return rc;
-  HeadArgs h = make_head(L, nz, 1, n);
+                     const ActorDraw* act, hipStream_t st) {
+  if (int rc = forward_torso(L, params, src, which, n, st)) return rc;
+  HeadArgs h = make_head(L, NetZ{{params, params, params}, {which, which, which}}, 1, n);
   h.fwd_only = 1;
   h.q = q_out;
+  if (act) {
+    h.act_out = act->out;
+    h.eps = act->eps;
+    h.act_seed = act->seed;
+    h.act_ctr = act->counter;
+  }
   DQZ_HIP(launch_head(h, n, st));
   DQZ_HIP(hipGetLastError());
   return DQZ_OK;
 }
 
 int dqz_forward(dqz_learner* L, const float* params, const uint8_t* states, int n, float* q_out, void* stream) {
-  if (!L || !params || !states || !q_out) return fail(DQZ_ERR_INVALID, "null argument");
-  if (n < 1 || n > L->cfg.batch) return fail(DQZ_ERR_INVALID, "n must be in [1, %d]", L->cfg.batch);
-  if (reinterpret_cast<uintptr_t>(states) % 16) return fail(DQZ_ERR_INVALID, "states must be 16-byte aligned");
-  Conv1Src src{nullptr, nullptr, nullptr, states, 0, UniformDraw{}};
-  return forward_q(L, params, src, 0, n, q_out, (hipStream_t)stream);
+  Conv1Src src;
+  if (int rc = forward_src(L, params, n, {.states = states, .q_out = q_out}, &src)) return rc;
+  return forward_q(L, params, src, 0, n, q_out, nullptr, (hipStream_t)stream);
 }
 
 int dqz_forward_slots(dqz_learner* L, const float* params, const dqz_store* S, const int32_t* slots, int n, int which,
                       float* q_out, void* stream) {
-  if (!L || !params || !slots || !q_out) return fail(DQZ_ERR_INVALID, "null argument");
-  if (int rc = check_store(S)) return rc;
-  if (n < 1 || n > L->cfg.batch) return fail(DQZ_ERR_INVALID, "n must be in [1, %d]", L->cfg.batch);
-  if (which != 0 && which != 1) return fail(DQZ_ERR_INVALID, "which must be 0 (s_tm1) or 1 (s_t)");
-  Conv1Src src{S->frames, S->fidx, slots, nullptr, 0, UniformDraw{}};
-  return forward_q(L, params, src, which, n, q_out, (hipStream_t)stream);
+  Conv1Src src;
+  const ForwardInput in{.from_store = true, .store = S, .slots = slots, .which = which, .q_out = q_out};
+  if (int rc = forward_src(L, params, n, in, &src)) return rc;
+  return forward_q(L, params, src, which, n, q_out, nullptr, (hipStream_t)stream);
 }
 
 int dqz_act(dqz_learner* L, const float* params, const uint8_t* states, int n, double epsilon, uint64_t seed,
             uint64_t counter, dqz_action* out, void* stream) {
-  if (!L || !params || !states || !out) return fail(DQZ_ERR_INVALID, "null argument");
-  if (n < 1 || n > L->cfg.batch) return fail(DQZ_ERR_INVALID, "n must be in [1, %d]", L->cfg.batch);
-  if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(DQZ_ERR_INVALID, "epsilon must be in [0, 1]");
-  const void *dstates = nullptr, *dout = nullptr;
-  if (int rc = device_view(states, &dstates, "states")) return rc;
-  if (int rc = device_view(out, &dout, "out")) return rc;
-  if (reinterpret_cast<uintptr_t>(dstates) % 16) return fail(DQZ_ERR_INVALID, "states must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const NetZ nz{{params, params, params}, {0, 0, 0}};
-  Conv1Src src{nullptr, nullptr, nullptr, static_cast<const uint8_t*>(dstates), 0, UniformDraw{}};
-  if (int rc = forward_impl(L, nz, 1, n, src, st, PhaseEvents{})) return rc;
-  HeadArgs h = make_head(L, nz, 1, n);
-  h.fwd_only = 1;
-  h.q = L->q;
-  h.act_out = static_cast<dqz_action*>(const_cast<void*>(dout));
-  h.eps = epsilon;
-  h.act_seed = seed;
-  h.act_ctr = counter;
-  DQZ_HIP(launch_head(h, n, st));
-  return DQZ_OK;
+  ActorDraw act{epsilon, seed, counter, out};
+  Conv1Src src;
+  if (int rc = forward_src(L, params, n, {.states = states, .act = &act}, &src)) return rc;
+  return forward_q(L, params, src, 0, n, L->q, &act, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -40,6 +40,22 @@ def rmsprop(learning_rate, decay=0.9, eps=1e-8, centered=False):
   return RMSPropConfig(learning_rate, decay, eps, centered)
 
 
+class AdamConfig:
+  """optax.adam(learning_rate, b1, b2, eps) stand-in (eps_root = 0)."""
+
+  def __init__(self, learning_rate, b1=0.9, b2=0.999, eps=1e-8, eps_root=0.0):
+    if eps_root != 0.0:
+      raise NotImplementedError('eps_root is not used by the reference')
+    self.learning_rate = float(learning_rate)
+    self.b1 = float(b1)
+    self.b2 = float(b2)
+    self.eps = float(eps)
+
+
+def adam(learning_rate, b1=0.9, b2=0.999, eps=1e-8, eps_root=0.0):
+  return AdamConfig(learning_rate, b1, b2, eps, eps_root)
+
+
 class ClipByGlobalNorm:
   """optax.clip_by_global_norm(max_norm) stand-in: the first stage of a chain."""
 
@@ -95,7 +111,14 @@ def is_centered_rmsprop(optimizer):
 class Learner:
   """Online/target params + optimizer moments in HBM and a libdqz handle."""
 
+  _h = None  # dqz_learner handle
   _opt_h = None  # dqz_optimizer handle; None: centered RMSProp, fused into the step
+  _act_in = None  # act()'s pinned input buffer, set up with the output's on its first call
+  # The handle that owns the native state (an attribute's name) and the entries
+  # that take it: what a subclass with another head names anew.
+  _OWNER = '_h'
+  _ENTRIES = dict(destroy='dqz_learner_destroy', forward='dqz_forward',
+                  forward_slots='dqz_forward_slots', act='dqz_act')
 
   def __init__(self, network: networks_lib.NetworkSpec, batch_size, algo='dqn',
                optimizer=None, grad_error_bound=1.0 / 32, device='cuda'):
@@ -105,62 +128,78 @@ class Learner:
       raise ValueError(
           "algo 'dqn' uses dqn_atari_network; 'double'/'per' use "
           'double_dqn_atari_network (shared bias)')
-    optimizer = optimizer or rmsprop(2.5e-4, 0.95, 0.01 / 32**2, True)
-    self.network = network
     self.algo = algo
+    self.grad_error_bound = float(grad_error_bound)
+    self._alloc_state(network, batch_size,
+                      optimizer or rmsprop(2.5e-4, 0.95, 0.01 / 32**2, True), device)
+    self.q_tm1 = torch.zeros((self.batch_size, network.num_actions),
+                             dtype=torch.float32, device=self.device)
+    self.td = torch.zeros((self.batch_size,), dtype=torch.float32, device=self.device)
+    self.loss = torch.zeros((1,), dtype=torch.float32, device=self.device)
+    handle = ctypes.c_void_p()
+    _native.check(_native.lib().dqz_learner_create(
+        ctypes.byref(self._learner_config(ALGOS[algo])), ctypes.byref(handle)))
+    self._h = handle
+    # Adam / plain RMSProp / a clipped chain: the step runs in gradient mode
+    # and dqz_optimizer_apply follows it (centered RMSProp stays fused).
+    if not is_centered_rmsprop(self.optimizer):
+      self._opt_h = self._create_optimizer(_native.lib().dqz_optimizer_create)
+
+  def _alloc_state(self, network, batch_size, optimizer, device):
+    """The flat state every head shares: parameters, moments, the step count
+    and their dqz_params, with the optimizer split into clip and base."""
+    self.network = network
     self.batch_size = int(batch_size)
     self.optimizer = optimizer
-    self.grad_error_bound = float(grad_error_bound)
+    self.clip_norm, self.base_optimizer = split_optimizer(optimizer)
     self.device = torch.device(device)
     self.offsets, self.sizes, self.total = network.layout()
     self.online = torch.zeros((self.total,), dtype=torch.float32, device=self.device)
     self.target = torch.zeros_like(self.online)
     self.mu = torch.zeros_like(self.online)
     self.nu = torch.zeros_like(self.online)
-    self.q_tm1 = torch.zeros((self.batch_size, network.num_actions),
-                             dtype=torch.float32, device=self.device)
-    self.td = torch.zeros((self.batch_size,), dtype=torch.float32, device=self.device)
-    self.loss = torch.zeros((1,), dtype=torch.float32, device=self.device)
-    self.clip_norm, base = split_optimizer(optimizer)
-    self.base_optimizer = base
-    cfg = _native.DqzLearnerConfig(
-        self.batch_size, network.num_actions, ALGOS[algo],
-        base.learning_rate, getattr(base, 'decay', 0.0), base.eps,
-        float(grad_error_bound))
-    handle = ctypes.c_void_p()
-    _native.check(_native.lib().dqz_learner_create(ctypes.byref(cfg),
-                                                   ctypes.byref(handle)))
-    self._h = handle
-    # Adam / plain RMSProp / a clipped chain: the step runs in gradient mode
-    # and dqz_optimizer_apply follows it (centered RMSProp stays fused).
-    self._opt_h = None
     self.count = torch.zeros((1,), dtype=torch.int32, device=self.device)
     self._gnorm = torch.zeros((1,), dtype=torch.float32, device=self.device)
-    if not is_centered_rmsprop(optimizer):
-      is_adam = isinstance(base, AdamConfig)
-      ocfg = _native.DqzOptimizerConfig(
-          _native.OPT_ADAM if is_adam else _native.OPT_RMSPROP,
-          base.learning_rate, getattr(base, 'b1', 0.0), getattr(base, 'b2', 0.0),
-          getattr(base, 'decay', 0.0), base.eps,
-          self.clip_norm if self.clip_norm is not None else 0.0,
-          network.num_actions, int(bool(network.shared_bias)))
-      oh = ctypes.c_void_p()
-      _native.check(_native.lib().dqz_optimizer_create(ctypes.byref(ocfg),
-                                                       ctypes.byref(oh)))
-      self._opt_h = oh
     self._params_c = _native.DqzParams(
         self.online.data_ptr(), self.target.data_ptr(), self.mu.data_ptr(),
         self.nu.data_ptr())
 
+  def _learner_config(self, algo_id):
+    base = self.base_optimizer
+    return _native.DqzLearnerConfig(
+        self.batch_size, self.network.num_actions, algo_id, base.learning_rate,
+        getattr(base, 'decay', 0.0), base.eps, self.grad_error_bound)
+
+  def _create_optimizer(self, create, *layout_args):
+    """A dqz_optimizer for (base optimizer, clip norm, network) from the
+    head's create function: create(config, *layout_args, out)."""
+    base = self.base_optimizer
+    ocfg = _native.DqzOptimizerConfig(
+        _native.OPT_ADAM if isinstance(base, AdamConfig) else _native.OPT_RMSPROP,
+        base.learning_rate, getattr(base, 'b1', 0.0), getattr(base, 'b2', 0.0),
+        getattr(base, 'decay', 0.0), base.eps,
+        self.clip_norm if self.clip_norm is not None else 0.0,
+        self.network.num_actions, int(bool(self.network.shared_bias)))
+    oh = ctypes.c_void_p()
+    _native.check(create(ctypes.byref(ocfg), *layout_args, ctypes.byref(oh)))
+    return oh
+
+  def _call(self, entry, *args):
+    """The head's own `entry` (_ENTRIES) on the handle that owns the state."""
+    fn = getattr(_native.lib(), self._ENTRIES[entry])
+    return fn(getattr(self, self._OWNER), *args)
+
   def __del__(self):
-    h = getattr(self, '_h', None)
-    if h is not None and h.value and _native is not None and _native._lib is not None:  # pylint: disable=protected-access
-      _native.lib().dqz_learner_destroy(h)
+    if _native is None or _native._lib is None:  # pylint: disable=protected-access
+      return
+    h = getattr(self, self._OWNER)
+    if h is not None and h.value:
+      self._call('destroy')
+      setattr(self, self._OWNER, None)
       self._h = None
-      oh = getattr(self, '_opt_h', None)
-      if oh is not None and oh.value:
-        _native.lib().dqz_optimizer_destroy(oh)
-        self._opt_h = None
+    if self._opt_h is not None and self._opt_h.value:
+      _native.lib().dqz_optimizer_destroy(self._opt_h)
+      self._opt_h = None
 
   # -- state -------------------------------------------------------------
 
@@ -221,14 +260,17 @@ class Learner:
 
   # -- hot path ------------------------------------------------------------
 
+  def _check_slots(self, slots, name='slots'):
+    if slots.dtype != torch.int32 or slots.numel() != self.batch_size:
+      raise ValueError('%s must be a device int32 tensor of batch size' % name)
+
   def step(self, store, slots, weights=None, stream=None, write_back=None):
     """One learner step on replay `slots` (device int32 [B]).
 
     write_back (PER only): (tree, cap, indices, alpha, max_seen_dev) — the
     priority write-back of this step's |td| (dqz_per_write_back's arguments)
     folded into the backward launch (dqz_learner_step_per)."""
-    if slots.dtype != torch.int32 or slots.numel() != self.batch_size:
-      raise ValueError('slots must be a device int32 tensor of batch size')
+    self._check_slots(slots)
     if self.algo == 'per' and weights is None:
       raise ValueError('PER step needs importance weights')
     if self._opt_h is not None:
@@ -261,8 +303,7 @@ class Learner:
     Draws exactly what `sample_uniform(base, size, capacity, B, seed,
     counter, ...)` would, writes them to `slots_out` and advances `counter`.
     """
-    if slots_out.dtype != torch.int32 or slots_out.numel() != self.batch_size:
-      raise ValueError('slots_out must be a device int32 tensor of batch size')
+    self._check_slots(slots_out, 'slots_out')
     if self._opt_h is not None:
       _native.check(_native.lib().dqz_learner_step_opt_uniform(
           self._h, ctypes.byref(self._params_c), store.c_ref(), int(base),
@@ -287,8 +328,7 @@ class Learner:
     probabilities and its choice, bit for bit — what
     logit_buffer.sample_exact(uniforms) draws — after three preparation
     launches over the buffer."""
-    if slots_out.dtype != torch.int32 or slots_out.numel() != self.batch_size:
-      raise ValueError('slots_out must be a device int32 tensor of batch size')
+    self._check_slots(slots_out, 'slots_out')
     if (counter is None) == (uniforms is None):
       raise ValueError('pass exactly one of counter (Philox) and uniforms')
     self._need_fused_rmsprop('step_logits')
@@ -320,8 +360,7 @@ class Learner:
 
   def grad(self, store, slots, weights=None, out=None, stream=None):
     """jax.grad(loss_fn) of the same step into a flat tensor (no update)."""
-    if slots.dtype != torch.int32 or slots.numel() != self.batch_size:
-      raise ValueError('slots must be a device int32 tensor of batch size')
+    self._check_slots(slots)
     out = torch.zeros_like(self.online) if out is None else out
     _native.check(_native.lib().dqz_learner_grad(
         self._h, ctypes.byref(self._params_c), store.c_ref(),
@@ -422,8 +461,8 @@ class Learner:
                       device=self.device)
     for i in range(0, n, self.batch_size):
       j = min(n, i + self.batch_size)
-      _native.check(_native.lib().dqz_forward(
-          self._h, _native.ptr(params), _native.ptr(states[i:j]), j - i,
+      _native.check(self._call(
+          'forward', _native.ptr(params), _native.ptr(states[i:j]), j - i,
           _native.ptr(out[i:j]), _native.stream_handle(stream)))
     return out
 
@@ -458,20 +497,21 @@ class Learner:
     return out[0] if observation.ndim == 3 else out
 
   def act(self, observation, epsilon, seed, counter, params=None):
-    """select_action on device (dqn/agent.py:121-131): (action, max_a q) for
-    one host uint8 [84,84,4] observation, the eps-greedy draw being number
-    `counter` of the Philox stream `seed` (dqz_act).  The observation is
-    read and the result written in place in pinned host buffers: one launch
-    chain and one stream synchronisation per call, no staging copies."""
-    if getattr(self, '_act_in', None) is None:
+    """select_action on device (dqn/agent.py:121-131, c51/agent.py:121-129):
+    (action, max_a q) for one host uint8 [84,84,4] observation, the
+    eps-greedy draw being number `counter` of the Philox stream `seed`
+    (dqz_act, dqz_c51_act).  The observation is read and the result written
+    in place in pinned host buffers: one launch chain and one stream
+    synchronisation per call, no staging copies."""
+    if self._act_in is None:
       self._act_in = torch.empty((1, 84, 84, 4), dtype=torch.uint8,
                                  pin_memory=True)
       self._act_in_np = self._act_in.numpy()
       self._act_out = torch.zeros((2,), dtype=torch.int32, pin_memory=True)
       self._act_out_np = self._act_out.numpy()
     self._act_in_np[0] = observation
-    _native.check(_native.lib().dqz_act(
-        self._h, _native.ptr(self._params_tensor(params)),
+    _native.check(self._call(
+        'act', _native.ptr(self._params_tensor(params)),
         ctypes.c_void_p(self._act_in.data_ptr()), 1, float(epsilon),
         int(seed) & (2**64 - 1), int(counter) & (2**64 - 1),
         ctypes.c_void_p(self._act_out.data_ptr()), _native.stream_handle()))
@@ -483,9 +523,9 @@ class Learner:
     n = int(slots.numel())
     out = torch.empty((n, self.network.num_actions), dtype=torch.float32,
                       device=self.device)
-    _native.check(_native.lib().dqz_forward_slots(
-        self._h, _native.ptr(params), store.c_ref(), _native.ptr(slots), n,
-        int(which), _native.ptr(out), _native.stream_handle(stream)))
+    _native.check(self._call(
+        'forward_slots', _native.ptr(params), store.c_ref(), _native.ptr(slots),
+        n, int(which), _native.ptr(out), _native.stream_handle(stream)))
     return out
 
 
@@ -497,22 +537,6 @@ def sample_uniform(base, size, capacity, n, seed, counter, out, stream=None):
   return out
 
 
-class AdamConfig:
-  """optax.adam(learning_rate, b1, b2, eps) stand-in (eps_root = 0)."""
-
-  def __init__(self, learning_rate, b1=0.9, b2=0.999, eps=1e-8, eps_root=0.0):
-    if eps_root != 0.0:
-      raise NotImplementedError('eps_root is not used by the reference')
-    self.learning_rate = float(learning_rate)
-    self.b1 = float(b1)
-    self.b2 = float(b2)
-    self.eps = float(eps)
-
-
-def adam(learning_rate, b1=0.9, b2=0.999, eps=1e-8, eps_root=0.0):
-  return AdamConfig(learning_rate, b1, b2, eps, eps_root)
-
-
 class C51Learner(Learner):
   """The categorical (C51) learner: `update` of c51/agent.py:109-117 and
   `select_action` of :121-129 on device (dqz_c51_*).
@@ -522,6 +546,11 @@ class C51Learner(Learner):
   head, in gradient mode, followed by the optimizer, so the optimizer is Adam
   or plain RMSProp, alone or behind clip_by_global_norm (the reference's chain,
   c51/run_atari.py:210-216, is the default)."""
+
+  _c51 = None  # dqz_c51 handle; it owns the dqz_learner behind _h
+  _OWNER = '_c51'
+  _ENTRIES = dict(destroy='dqz_c51_destroy', forward='dqz_c51_forward',
+                  forward_slots='dqz_c51_forward_slots', act='dqz_c51_act')
 
   def __init__(self, network: networks_lib.C51NetworkSpec, batch_size,
                optimizer=None, device='cuda'):
@@ -535,85 +564,36 @@ class C51Learner(Learner):
           'RMSProp exists only fused into the DQN step; use adam(...), '
           'rmsprop(..., centered=False) or chain(clip_by_global_norm(c), one '
           'of them)')
-    self.clip_norm, base = split_optimizer(optimizer)
-    self._h = self._c51 = self._opt_h = None
-    self.network = network
     self.algo = 'c51'
-    self.batch_size = int(batch_size)
-    self.optimizer = optimizer
-    self.base_optimizer = base
     self.grad_error_bound = 0.0
-    self.device = torch.device(device)
-    self.offsets, self.sizes, self.total = network.layout()
+    self._alloc_state(network, batch_size, optimizer, device)
     b, a, n = self.batch_size, network.num_actions, network.num_atoms
     f32 = dict(dtype=torch.float32, device=self.device)
-    self.online = torch.zeros((self.total,), **f32)
-    self.target = torch.zeros_like(self.online)
-    self.mu = torch.zeros_like(self.online)
-    self.nu = torch.zeros_like(self.online)
     self.support = torch.from_numpy(network.support).to(self.device)
     self.logits_a = torch.zeros((b, n), **f32)
     self.q = torch.zeros((2, b, a), **f32)
     self.loss_b = torch.zeros((b,), **f32)
     self.loss = torch.zeros((1,), **f32)
     self.a_star = torch.zeros((b,), dtype=torch.int32, device=self.device)
-    self.count = torch.zeros((1,), dtype=torch.int32, device=self.device)
-    self._gnorm = torch.zeros((1,), **f32)
     lib = _native.lib()
-    cfg = _native.DqzLearnerConfig(b, a, _native.ALGO_DQN, base.learning_rate,
-                                   getattr(base, 'decay', 0.0), base.eps, 0.0)
     handle = ctypes.c_void_p()
-    _native.check(lib.dqz_c51_create(ctypes.byref(cfg), n,
-                                     _native.ptr(self.support),
-                                     ctypes.byref(handle)))
+    _native.check(lib.dqz_c51_create(
+        ctypes.byref(self._learner_config(_native.ALGO_DQN)), n,
+        _native.ptr(self.support), ctypes.byref(handle)))
     self._c51 = handle
     inner = ctypes.c_void_p()
     _native.check(lib.dqz_c51_learner(handle, ctypes.byref(inner)))
     self._h = inner  # owned by the c51 handle: sync_status, fetch_activations
-    is_adam = isinstance(base, AdamConfig)
-    ocfg = _native.DqzOptimizerConfig(
-        _native.OPT_ADAM if is_adam else _native.OPT_RMSPROP,
-        base.learning_rate, getattr(base, 'b1', 0.0), getattr(base, 'b2', 0.0),
-        getattr(base, 'decay', 0.0), base.eps,
-        self.clip_norm if self.clip_norm is not None else 0.0, a, 0)
-    oh = ctypes.c_void_p()
-    _native.check(lib.dqz_c51_optimizer_create(ctypes.byref(ocfg), n,
-                                               ctypes.byref(oh)))
-    self._opt_h = oh
-    self._params_c = _native.DqzParams(
-        self.online.data_ptr(), self.target.data_ptr(), self.mu.data_ptr(),
-        self.nu.data_ptr())
-
-  def __del__(self):
-    if _native is None or _native._lib is None:  # pylint: disable=protected-access
-      return
-    h = getattr(self, '_c51', None)
-    if h is not None and h.value:
-      _native.lib().dqz_c51_destroy(h)
-      self._c51 = self._h = None
-    oh = getattr(self, '_opt_h', None)
-    if oh is not None and oh.value:
-      _native.lib().dqz_optimizer_destroy(oh)
-      self._opt_h = None
+    self._opt_h = self._create_optimizer(lib.dqz_c51_optimizer_create, n)
 
   def load_opt_state(self, state):
     """Restores what opt_state() returned; a centered-RMSProp state (a DQN
     agent's checkpoint) is refused by name."""
-    inner = state
-    if (isinstance(inner, tuple) and len(inner) == 2
-        and isinstance(inner[0], tuple) and len(inner[0]) == 0):
-      inner = inner[1]
-    first = inner[0] if isinstance(inner, tuple) and inner else None
-    fields = getattr(first, '_fields', ())  # (a tuple's own .count is a method)
-    if 'mu' in fields and 'nu' in fields and 'count' not in fields:
+    if optim_state.is_rmsprop_state(state):
       raise ValueError(
           'a centered-RMSProp state cannot restore a C51 learner (its '
           'optimizer is %s)' % type(self.base_optimizer).__name__)
     super().load_opt_state(state)
-
-  def _check_slots(self, slots):
-    if slots.dtype != torch.int32 or slots.numel() != self.batch_size:
-      raise ValueError('slots must be a device int32 tensor of batch size')
 
   def step(self, store, slots, stream=None):  # pylint: disable=arguments-differ
     """One learner step on replay `slots` (device int32 [B])."""
@@ -665,48 +645,6 @@ class C51Learner(Learner):
     names = list(_native.PHASE_NAMES)
     names[4], names[8], names[7] = 'c51_logits', 'c51_head', 'c51_fc2_grad'
     return {n: float(t) for n, t in zip(names, out) if t > 0.0}
-
-  def q_values(self, states, params=None, stream=None):
-    """network.apply(params, s).q_values for uint8 [n,84,84,4] device states."""
-    params = self.online if params is None else params
-    states = states.contiguous()
-    n = int(states.shape[0])
-    out = torch.empty((n, self.network.num_actions), dtype=torch.float32,
-                      device=self.device)
-    for i in range(0, n, self.batch_size):
-      j = min(n, i + self.batch_size)
-      _native.check(_native.lib().dqz_c51_forward(
-          self._c51, _native.ptr(params), _native.ptr(states[i:j]), j - i,
-          _native.ptr(out[i:j]), _native.stream_handle(stream)))
-    return out
-
-  def q_values_slots(self, store, slots, which, params=None, stream=None):
-    params = self.online if params is None else params
-    n = int(slots.numel())
-    out = torch.empty((n, self.network.num_actions), dtype=torch.float32,
-                      device=self.device)
-    _native.check(_native.lib().dqz_c51_forward_slots(
-        self._c51, _native.ptr(params), store.c_ref(), _native.ptr(slots), n,
-        int(which), _native.ptr(out), _native.stream_handle(stream)))
-    return out
-
-  def act(self, observation, epsilon, seed, counter, params=None):
-    """select_action on device (c51/agent.py:121-129): (action, max_a
-    q_values), as Learner.act."""
-    if getattr(self, '_act_in', None) is None:
-      self._act_in = torch.empty((1, 84, 84, 4), dtype=torch.uint8,
-                                 pin_memory=True)
-      self._act_in_np = self._act_in.numpy()
-      self._act_out = torch.zeros((2,), dtype=torch.int32, pin_memory=True)
-      self._act_out_np = self._act_out.numpy()
-    self._act_in_np[0] = observation
-    _native.check(_native.lib().dqz_c51_act(
-        self._c51, _native.ptr(self._params_tensor(params)),
-        ctypes.c_void_p(self._act_in.data_ptr()), 1, float(epsilon),
-        int(seed) & (2**64 - 1), int(counter) & (2**64 - 1),
-        ctypes.c_void_p(self._act_out.data_ptr()), _native.stream_handle()))
-    torch.cuda.current_stream(self.device).synchronize()
-    return int(self._act_out_np[0]), float(self._act_out_np.view(np.float32)[1])
 
   def _no_fused_draw(self, *unused_args, **unused_kwargs):
     raise NotImplementedError(

@@ -99,6 +99,19 @@ def rmsprop_moments(opt_state):
   return mu, nu
 
 
+def is_rmsprop_state(opt_state):
+  """Whether opt_state is a rmsprop_state by its fields (a pickled one too),
+  alone or behind a clip's empty state (chained_state).  An Adam state, which
+  also carries mu and nu, is not; neither is the round-2 (mu, nu) pair."""
+  inner = opt_state
+  if (isinstance(inner, tuple) and len(inner) == 2
+      and isinstance(inner[0], tuple) and len(inner[0]) == 0):
+    inner = inner[1]
+  first = inner[0] if isinstance(inner, tuple) and inner else None
+  fields = getattr(first, '_fields', ())  # (a tuple's own .count is a method)
+  return 'mu' in fields and 'nu' in fields and 'count' not in fields
+
+
 def adam_state(count, mu, nu):
   return (ScaleByAdamState(count=np.int32(count), mu=mu, nu=nu), EmptyState())
 

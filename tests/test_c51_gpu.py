@@ -136,11 +136,11 @@ def _check_conditions(case, ref=None, slots=None, single=True):
     assert ref['m'][i][-1] == pytest.approx(1.0, abs=1e-12)
 
 
-def _device(case, device, batch=None, clip=CLIP):
+def _device(case, device, batch=None, clip=CLIP, optimizer=None):
   from dqn_mgsc_zoo_amd import learner as learner_lib
   from dqn_mgsc_zoo_amd import store as store_lib
   lrn = learner_lib.C51Learner(case['net'], len(case['slots']) if batch is None else batch,
-                               optimizer=_optimizer(clip), device=device)
+                               optimizer=optimizer or _optimizer(clip), device=device)
   lrn.set_params(case['online'], case['target'])
   st = store_lib.FrameStore(256, 640)
   for name, arr in case['host'].items():
@@ -334,6 +334,41 @@ def test_a_step_is_bit_reproducible(device):
   for x, y in zip(*runs):
     assert np.array_equal(x, y)
   assert not np.array_equal(runs[0][0], _bits(snap[0]))
+
+
+BINDING_CLIP = 0.1  # below the (5, 3, 7) case's gradient norm (0.415 in the oracle), so the clip scales
+
+
+@pytest.mark.parametrize('optimizer', ['clip_adam', 'rmsprop'])
+def test_a_step_is_its_gradient_then_apply(device, optimizer):
+  """tests/test_optimizers_gpu.py's test_step_opt_is_grad_then_apply for the
+  categorical head: C51Learner.step leaves the bits of C51Learner.grad
+  followed by dqz_optimizer_apply on the learner's own optimizer handle."""
+  from dqn_mgsc_zoo_amd import _native
+  from dqn_mgsc_zoo_amd import learner as learner_lib
+  case = _case(5, 3, 7)
+  opt = _optimizer(BINDING_CLIP) if optimizer == 'clip_adam' else learner_lib.rmsprop(LR, 0.95, 1e-6, centered=False)
+  lrn, st = _device(case, device, optimizer=opt)
+  slots = torch.from_numpy(case['slots']).to(device)
+  for step in range(2):  # the second from carried moments
+    snap = _snapshot(lrn)
+    lrn.step(st, slots)
+    after = _snapshot(lrn)
+    gn = lrn.grad_norm().clone()
+    _restore(lrn, snap)
+    g = lrn.grad(st, slots)
+    _native.check(_native.lib().dqz_optimizer_apply(
+        lrn._opt_h, _native.ptr(lrn.online), _native.ptr(g), _native.ptr(lrn.mu),  # pylint: disable=protected-access
+        _native.ptr(lrn.nu), _native.ptr(lrn.count), _native.stream_handle()))
+    torch.cuda.synchronize()
+    for x, y in zip(after, _snapshot(lrn)):
+      assert torch.equal(x, y), step
+    assert torch.equal(gn, lrn.grad_norm())
+    torch.cuda.synchronize()
+    assert not torch.equal(snap[0], after[0])
+    if optimizer == 'clip_adam':
+      assert float(gn.item()) > BINDING_CLIP and int(lrn.count.item()) == step + 1
+    assert lrn.sync_status() == 0
 
 
 def test_three_captured_steps_equal_three_eager_steps(device):

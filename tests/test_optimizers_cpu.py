@@ -214,3 +214,37 @@ def test_learner_state_shape_follows_its_optimizer():
   st = r.opt_state()
   assert type(st[0]).__name__ == 'ScaleByRmsState' and st[0].nu is nu
   r.load_opt_state(st)
+
+
+class _FakeC51Learner(learner_lib.C51Learner):
+  """C51Learner.load_opt_state without a device, in _FakeLearner's manner (a
+  subclass, since that method reaches Learner's through super())."""
+
+  __init__ = _FakeLearner.__init__
+  params_tree = _FakeLearner.params_tree
+  set_opt_state = _FakeLearner.set_opt_state
+
+
+def test_c51_learner_refuses_a_centered_rmsprop_state_and_restores_its_own():
+  rng = np.random.default_rng(5)
+  mu, nu = _tree(rng), _tree(rng)
+  clipped = learner_lib.chain(learner_lib.clip_by_global_norm(10.0), learner_lib.adam(1e-3))
+  a = _FakeC51Learner(clipped)
+  centered = os_.rmsprop_state(mu, nu)
+  for bad in (centered, pickle.loads(pickle.dumps(centered)), os_.chained_state(centered)):
+    with pytest.raises(ValueError, match='centered-RMSProp'):
+      a.load_opt_state(bad)
+  assert not a.trees and a.count.v == 0
+  # a clipped-Adam learner restores its own chained state, count included
+  src = _FakeC51Learner(clipped)
+  src.trees = {'mu': mu, 'nu': nu}
+  src.count.v = 11
+  st = src.opt_state()
+  assert st[0] == os_.EmptyState() and type(st[1][0]).__name__ == 'ScaleByAdamState'
+  a.load_opt_state(pickle.loads(pickle.dumps(st)))
+  assert a.count.v == 11
+  np.testing.assert_array_equal(a.trees['mu']['conv']['w'], mu['conv']['w'])
+  np.testing.assert_array_equal(a.trees['nu']['linear']['b'], nu['linear']['b'])
+  # an unchained Adam state is not taken for the clipped learner's
+  with pytest.raises(ValueError):
+    a.load_opt_state(os_.adam_state(11, mu, nu))
