@@ -70,6 +70,18 @@ class DqzLearnerConfig(ctypes.Structure):
   ]
 
 
+META_ZVP_PARTS = 7  # DQZ_META_ZVP_PARTS
+META_HPART_CHUNKS = 196  # DQZ_META_HPART_CHUNKS
+# dqz_meta_stages, in the header's field order
+META_STAGE_FIELDS = ('G', 'thp', 'mu1', 'nu1', 'J', 'GQ', 'HQ', 'ty1', 'ty2', 'ty3',
+                     'hpart', 'td4', 'td3', 'td2', 'td1', 's1', 'p', 's', 'zv1',
+                     'zv2', 'zv3', 'zvp')
+
+
+class DqzMetaStages(ctypes.Structure):
+  _fields_ = [(name, ctypes.c_void_p) for name in META_STAGE_FIELDS]
+
+
 class DqzMetaConfig(ctypes.Structure):
   _fields_ = [
       ('meta_batch', ctypes.c_int),
@@ -342,6 +354,8 @@ SIGNATURES = {
     'dqz_meta_outputs': (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     'dqz_meta_sync_status': (_int, [_vp, _vp]),
     'dqz_meta_debug_stall': (_int, [_vp, _int, ctypes.c_uint]),
+    'dqz_meta_debug_learner': (_int, [_vp, _int, ctypes.POINTER(_vp)]),
+    'dqz_meta_debug_stages': (_int, [_vp, _vp, _vp]),
 }
 
 _lib = None

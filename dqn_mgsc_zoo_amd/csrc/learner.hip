@@ -1190,7 +1190,7 @@ struct dqz_meta {
   dqz_learner* lm;   // meta batch learner (B = C)
   dqz_learner* l1;   // one-transition learner (B = 1)
   int64_t total;
-  float *G, *thp, *mu1, *nu1, *J;  // [total] each; G also holds g', thp also holds v
+  float *G, *thp, *mu1, *nu1, *J;  // [total] each; first order: G is overwritten with v (the second order's v: HQ)
   float *zv1, *zv2, *zv3, *zvp;    // tangent forward outputs
   float *x, *p, *s, *dl, *loss, *loss_part, *td;  // p, s, td: [K C] (p = 0 past M)
   int32_t* slots_pad;                                // [K C]
@@ -1294,7 +1294,7 @@ struct MetaRun {
   // the meta stage the gradient epilogues apply (Rms::meta, set by each pass) and its buffers
   Rms epi{.thp = H->thp, .mu1 = H->mu1, .nu1 = H->nu1, .J = H->J, .sq_part = H->loss_part};
   dqz_params P1{H->thp, P->online, nullptr, nullptr};  // the theta' pass: online = theta', target = theta
-  const float* v = H->cfg.second_order ? H->thp : H->G;  // the tangent direction the theta' pass leaves
+  const float* v = H->cfg.second_order ? H->HQ : H->G;  // the tangent direction the theta' pass leaves
   // the theta' pass's partial sums of u'^2 (the fc1 dW blocks', then the update's) that the Adam stage folds
   const int A = H->cfg.num_actions;
   int nloss = 4 * (FLAT / 16) + (int)update_blocks(H->l1->sz, A, H->l1->shared_bias ? 1 : A);
@@ -1348,7 +1348,8 @@ static int meta_theta_first(MetaRun& m) {
 
 // theta' pass, second order: grad q[a] (unit cotangent) -> GQ, consumed where it is formed (Rms::meta3): v_dir ->
 // mu1, w -> nu1, block sums of u'^2 and grad q . w.  The one-sample learner keeps the primal activations, the
-// backward signals and td' for the HVP, whose epilogue combines v -> thp (theta' is no longer needed).
+// backward signals and td' for the HVP, whose epilogue combines v -> HQ.  Not -> thp: hvp_l3_kernel's b1 blocks read
+// theta''s conv2 weights from thp while its conv2 row blocks store v's conv2 leaf, with no hand-off between them.
 static int meta_theta_second(MetaRun& m) {
   dqz_meta* H = m.H;
   dqz_learner* L1 = H->l1;
@@ -1360,13 +1361,14 @@ static int meta_theta_second(MetaRun& m) {
   if (int rc = step_impl(L1, &m.P1, m.S1, {.slots = m.online_slot, .gout = H->GQ, .unit = 1, .meta_epi = &m.epi,
                                            .xout = H->x1}, m.stream))
     return rc;
-  // (vdir .. vout: meta_combine in hvp_g's epilogue, v = v_dir + J (alpha s1 grad q - clip(td') H w) -> thp)
+  // (vdir .. vout: meta_combine in hvp_g's epilogue, v = v_dir + J (alpha s1 grad q - clip(td') H w) -> HQ; hq, the
+  // raw H_q w of a null vout, names the same buffer and is not written)
   HvpArgs hv{.x = H->x1, .rec = reinterpret_cast<const float4*>(L1->rec), .th = H->thp, .tw = H->nu1,
              .A = H->cfg.num_actions, .y1 = L1->y1, .y2 = L1->y2, .y3 = L1->y3, .h = L1->h1,
              .d1 = L1->dy1, .d2 = L1->dy2, .d3 = L1->dy3, .d4 = L1->dz1,
              .ty1 = H->ty1, .ty2 = H->ty2, .ty3 = H->ty3, .td4 = H->td4, .td3 = H->td3, .td2 = H->td2, .td1 = H->td1,
              .hq = H->HQ, .part = H->hpart, .s1_part = H->s1_part, .s1_nparts = m.nloss, .s1 = H->s1,
-             .vdir = H->mu1, .J = H->J, .gq = H->GQ, .td = L1->td, .bound = H->cfg.grad_error_bound, .vout = H->thp};
+             .vdir = H->mu1, .J = H->J, .gq = H->GQ, .td = L1->td, .bound = H->cfg.grad_error_bound, .vout = H->HQ};
   for (int i = 0; i < 10; ++i) hv.off[i] = L1->off[i];
   // ddot1's in-launch hand-off; a timeout lands in the one-transition learner's error word
   hv.td1_pub = Handoff{H->word(kMetaDdot1Cnt), H->word(kMetaDdot1Ack), L1->sync + sync_of(L1).err(), HVP_B1, HVP_G_C1,
@@ -1512,6 +1514,54 @@ int dqz_meta_debug_stall(dqz_meta* H, int poison, unsigned spin_max) {
     DQZ_HIP(hipMemcpy(H->word(kMetaDdot1Cnt), &p, sizeof(p), hipMemcpyHostToDevice));
     DQZ_HIP(hipMemcpy(H->word(kMetaAdamEntry), &p, sizeof(p), hipMemcpyHostToDevice));
   }
+  return DQZ_OK;
+}
+
+int dqz_meta_debug_learner(dqz_meta* H, int which, dqz_learner** out) {
+  if (!H || !out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (which != 0 && which != 1) return fail(DQZ_ERR_INVALID, "which must be 0 (batch) or 1 (one transition)");
+  *out = which ? H->l1 : H->lm;
+  return DQZ_OK;
+}
+
+static_assert(DQZ_META_ZVP_PARTS == FC1_S && DQZ_META_HPART_CHUNKS == HVP_T4_CHUNKS, "dqz.h restates the partial counts");
+
+int dqz_meta_debug_stages(dqz_meta* H, const dqz_meta_stages* o, void* stream) {
+  if (!H || !o) return fail(DQZ_ERR_INVALID, "null argument");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t T = H->total, C = H->C, KC = (int64_t)H->K * C;
+  // kind 1: second-order buffers; kind 2: written by the chunked tangent stage only
+  const struct {
+    float* dst;
+    const float* src;
+    int64_t n;
+    int kind;
+    const char* name;
+  } rows[] = {{o->G, H->G, T, 0, "G"},       {o->thp, H->thp, T, 0, "thp"},
+              {o->mu1, H->mu1, T, 0, "mu1"}, {o->nu1, H->nu1, T, 0, "nu1"},
+              {o->J, H->J, T, 0, "J"},       {o->GQ, H->GQ, T, 1, "GQ"},
+              {o->HQ, H->HQ, T, 1, "HQ"},    {o->ty1, H->ty1, (int64_t)C1M * C1CO, 1, "ty1"},
+              {o->ty2, H->ty2, (int64_t)C2M * C2CO, 1, "ty2"},
+              {o->ty3, H->ty3, FLAT, 1, "ty3"},
+              {o->hpart, H->hpart, (int64_t)HVP_T4_CHUNKS * HID, 1, "hpart"},
+              {o->td4, H->td4, HID, 1, "td4"},
+              {o->td3, H->td3, FLAT, 1, "td3"},
+              {o->td2, H->td2, (int64_t)C2M * C2CO, 1, "td2"},
+              {o->td1, H->td1, (int64_t)C1M * C1CO, 1, "td1"},
+              {o->s1, H->s1, 1, 1, "s1"},    {o->p, H->p, KC, 0, "p"},
+              {o->s, H->s, KC, 0, "s"},      {o->zv1, H->zv1, C * C1M * C1CO, 2, "zv1"},
+              {o->zv2, H->zv2, C * C2M * C2CO, 2, "zv2"},
+              {o->zv3, H->zv3, C * FLAT, 2, "zv3"},
+              {o->zvp, H->zvp, (int64_t)FC1_S * C * HID, 2, "zvp"}};
+  for (const auto& r : rows) {
+    if (!r.dst) continue;
+    if (r.kind == 1 && !H->cfg.second_order)
+      return fail(DQZ_ERR_INVALID, "%s exists only in a second-order meta handle", r.name);
+    if (r.kind == 2 && H->K == 1)
+      return fail(DQZ_ERR_INVALID, "%s is written only by a meta batch of more than one chunk", r.name);
+  }
+  for (const auto& r : rows)
+    if (r.dst) DQZ_HIP(hipMemcpyAsync(r.dst, r.src, sizeof(float) * r.n, hipMemcpyDeviceToDevice, st));
   return DQZ_OK;
 }
 

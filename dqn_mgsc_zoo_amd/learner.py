@@ -654,6 +654,26 @@ class C51Learner(Learner):
   step_uniform = step_logits = step_per_draw = _no_fused_draw
 
 
+class _BorrowedLearner:
+  """A dqz_learner the meta handle owns (MetaLearner.debug_learners): what
+  Learner.fetch_activations and Learner.fetch_outputs need, nothing else.
+  Keeps its MetaLearner alive; never destroys the handle."""
+
+  def __init__(self, meta, handle, batch_size):
+    self._owner = meta
+    self._h = handle
+    self.batch_size = batch_size
+    self.network = meta.learner.network
+    self.device = meta.learner.device
+    f32 = dict(dtype=torch.float32, device=self.device)
+    self.q_tm1 = torch.zeros((batch_size, self.network.num_actions), **f32)
+    self.td = torch.zeros((batch_size,), **f32)
+    self.loss = torch.zeros((1,), **f32)
+
+  fetch_activations = Learner.fetch_activations
+  fetch_outputs = Learner.fetch_outputs
+
+
 class MetaLearner:
   """MGSC meta-update on device (dqn_mgsc_batched/agent.py:104-220, 302-334).
 
@@ -779,6 +799,46 @@ class MetaLearner:
     meta handle at `spin_max` polls (0 restores the default) and, with
     `poison`, make the next update's HVP ddot1 and Adam entry waits run out."""
     _native.check(_native.lib().dqz_meta_debug_stall(self._h, int(bool(poison)), int(spin_max)))
+
+  def debug_learners(self):
+    """Diagnostic (dqz_meta_debug_learner): (batch learner, one-transition
+    learner) as light wrappers of the meta handle's own learners, on which
+    fetch_activations and fetch_outputs work as on a Learner.  The batch
+    learner holds the last chunk's forward, p-weighted backward signals and
+    td; the one-transition learner the pass at theta' (after a second-order
+    update its backward signals are the unit-cotangent ones of q[a])."""
+    out = []
+    for which, b in ((0, min(self.meta_batch_size, 256)), (1, 1)):
+      h = ctypes.c_void_p()
+      _native.check(_native.lib().dqz_meta_debug_learner(self._h, which, ctypes.byref(h)))
+      out.append(_BorrowedLearner(self, h, b))
+    return tuple(out)
+
+  def fetch_stages(self, stream=None):
+    """Diagnostic (dqz_meta_debug_stages): the stage buffers of the most
+    recent update as a dict of fresh device tensors (include/dqz.h
+    dqz_meta_stages says what each holds after which kind of update): G, thp,
+    mu1, nu1, J [T]; p, s [K C]; second order also GQ, HQ [T], ty1 [400,32],
+    ty2 [81,64], ty3 [3136], hpart [196,512], td4 [512], td3 [3136], td2
+    [81,64], td1 [400,32], s1 [1]; more than one chunk also zv1 [C,400,32],
+    zv2 [C,81,64], zv3 [C,3136], zvp [7,C,512] of the last chunk."""
+    t = int(self.learner.online.numel())
+    c = min(self.meta_batch_size, 256)
+    k = -(-self.meta_batch_size // c)
+    shapes = dict(G=(t,), thp=(t,), mu1=(t,), nu1=(t,), J=(t,), p=(k * c,), s=(k * c,))
+    if self.second_order:
+      shapes.update(GQ=(t,), HQ=(t,), ty1=(400, 32), ty2=(81, 64), ty3=(3136,),
+                    hpart=(_native.META_HPART_CHUNKS, 512), td4=(512,), td3=(3136,),
+                    td2=(81, 64), td1=(400, 32), s1=(1,))
+    if k > 1:
+      shapes.update(zv1=(c, 400, 32), zv2=(c, 81, 64), zv3=(c, 3136),
+                    zvp=(_native.META_ZVP_PARTS, c, 512))
+    out = {n: torch.empty(s, dtype=torch.float32, device=self.learner.device)
+           for n, s in shapes.items()}
+    req = _native.DqzMetaStages(**{n: v.data_ptr() for n, v in out.items()})
+    _native.check(_native.lib().dqz_meta_debug_stages(
+        self._h, ctypes.byref(req), _native.stream_handle(stream)))
+    return out
 
   def get_state(self):
     """optax.adam's state, (ScaleByAdamState(count, mu, nu), EmptyState()),

@@ -825,6 +825,54 @@ int dqz_meta_sync_status(dqz_meta* meta, int* status);
  * Synchronises the device. */
 int dqz_meta_debug_stall(dqz_meta* meta, int poison, unsigned spin_max);
 
+/* Diagnostic (tests): a borrowed handle of one of the meta handle's two
+ * learners (owned by `meta`, never destroyed by the caller), after the
+ * precedent of dqz_c51_learner.  which = 0: the batch learner (B = min(M,
+ * 256)), which holds the last chunk's forward, its p-weighted backward
+ * signals (dz1 .. dy1 already carry p_i) and td.  which = 1: the
+ * one-transition learner (B = 1) at theta' (copy 0 = theta'(s_tm1), copy 1 =
+ * theta(s_t)): y1 .. h1, td' and, after a second-order update, the
+ * unit-cotangent backward signals d4 .. d1 of q[a] (first order: those of the
+ * loss).  dqz_learner_debug_activations and dqz_learner_outputs apply. */
+int dqz_meta_debug_learner(dqz_meta* meta, int which, dqz_learner** out);
+
+/* The stage buffers dqz_meta_debug_stages copies out (device pointers, any
+ * may be NULL).  T = the parameter count of dqz_param_layout (padded total),
+ * C = min(M, 256) the chunk size, K = ceil(M / C) the chunk count.  What each
+ * holds after an update:
+ *   first order   G: v = dL/dG = -2 u' J (G itself is not kept); thp, mu1,
+ *                 nu1: theta', mu', nu'; J: du/dG.
+ *   second order  G: G = sum_i p_i g_i; thp: theta'; J; mu1: v_dir; nu1: w
+ *                 (the HVP's tangent); GQ: grad q[a] at theta'; HQ: v =
+ *                 v_dir + J (alpha s1 grad q - clip(td') H_q w).
+ *   K > 1         the batch learner and zv1 .. zvp hold the last chunk only.
+ * GQ .. s1 exist only in a second-order handle and zv1 .. zvp are written
+ * only when K > 1: asking for one the configuration does not have is refused
+ * (DQZ_ERR_INVALID). */
+#define DQZ_META_ZVP_PARTS 7  /* fc1 split-K partials of the tangent forward */
+#define DQZ_META_HPART_CHUNKS 196  /* K-chunks of the HVP's fc1 tangent */
+typedef struct dqz_meta_stages {
+  float *G, *thp, *mu1, *nu1, *J; /* [T] each, parameter layout */
+  float *GQ, *HQ;                 /* [T] each (second order) */
+  /* the HVP's tangents of the one transition (second order), ReLU masks
+   * applied: forward ty1 [400][32], ty2 [81][64], ty3 [3136]; hpart
+   * [DQZ_META_HPART_CHUNKS][512], whose sum over the chunks is the fc1
+   * tangent pre-activation without its bias; backward td4 [512], td3 [3136],
+   * td2 [81][64], td1 [400][32] */
+  float *ty1, *ty2, *ty3, *hpart, *td4, *td3, *td2, *td1;
+  float *s1;                      /* [1] grad q . w (second order) */
+  float *p, *s;                   /* [K C]: p = softmax(logits[pos]), 0 past M; s_i = p_i v . g_i (K > 1: 0 past M) */
+  /* K > 1, last chunk: the tangent forward V y + vb of the batch learner's
+   * activations, zv1 [C][400][32], zv2 [C][81][64], zv3 [C][3136], and the
+   * fc1 partials zvp [DQZ_META_ZVP_PARTS][C][512] (no bias) */
+  float *zv1, *zv2, *zv3, *zvp;
+} dqz_meta_stages;
+
+/* Diagnostic (tests): device-to-device copies of the last meta-update's stage
+ * buffers, ordered on `stream`; no kernel is launched and nothing the next
+ * update reads is written. */
+int dqz_meta_debug_stages(dqz_meta* meta, const dqz_meta_stages* out, void* stream);
+
 /* ---- Atari observation preprocessing (processors.py:421-505) -----------
  * The observation branch of processors.atari on device: element-wise max of
  * the last n RGB frames (np.max over the pooled frames), rgb2y
