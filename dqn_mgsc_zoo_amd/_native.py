@@ -279,6 +279,39 @@ SIGNATURES = {
         _int, [_vp, _vp, _vp, _int, ctypes.c_double, ctypes.c_uint64,
                ctypes.c_uint64, _vp, _vp]),
     'dqz_c51_debug_check': (_int, [_int, ctypes.c_uint]),
+    'dqz_qr_param_layout': (
+        _int,
+        [_int, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+         ctypes.POINTER(_i64)],
+    ),
+    'dqz_qr_optimizer_create': (
+        _int, [ctypes.POINTER(DqzOptimizerConfig), _int, ctypes.POINTER(_vp)]),
+    'dqz_qr_create': (
+        _int, [ctypes.POINTER(DqzLearnerConfig), _int, _vp, ctypes.c_float,
+               ctypes.POINTER(_vp)]),
+    'dqz_qr_destroy': (_int, [_vp]),
+    'dqz_qr_learner': (_int, [_vp, ctypes.POINTER(_vp)]),
+    'dqz_qr_step': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
+         _vp, _vp]),
+    'dqz_qr_grad': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
+         _vp]),
+    'dqz_qr_outputs': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dqz_qr_debug': (_int, [_vp, _vp, _vp, _vp]),
+    'dqz_qr_profile': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
+         _int, ctypes.POINTER(ctypes.c_float), _vp]),
+    'dqz_qr_forward': (_int, [_vp, _vp, _vp, _int, _vp, _vp]),
+    'dqz_qr_forward_slots': (
+        _int, [_vp, _vp, ctypes.POINTER(DqzStore), _vp, _int, _int, _vp, _vp]),
+    'dqz_qr_act': (
+        _int, [_vp, _vp, _vp, _int, ctypes.c_double, ctypes.c_uint64,
+               ctypes.c_uint64, _vp, _vp]),
+    'dqz_qr_debug_check': (_int, [_int, ctypes.c_uint]),
     'dqz_learner_grad': (
         _int,
         [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
@@ -450,7 +483,17 @@ def c51_param_layout(num_actions, num_atoms):
   return list(offs), list(sizes), int(total.value)
 
 
-# dqz_c51_debug_check's request bits (DQZ_C51_REQ_*)
+def qr_param_layout(num_actions, num_quantiles):
+  """(offsets, sizes, total) of the quantile network's flat buffer."""
+  offs = (_i64 * NUM_LEAVES)()
+  sizes = (_i64 * NUM_LEAVES)()
+  total = _i64()
+  check(lib().dqz_qr_param_layout(
+      int(num_actions), int(num_quantiles), offs, sizes, ctypes.byref(total)))
+  return list(offs), list(sizes), int(total.value)
+
+
+# dqz_c51_debug_check's and dqz_qr_debug_check's request bits (DQZ_C51_REQ_*)
 C51_REQ = dict(weights=1, per_draw=2, uniform_draw=4, logit_draw=8,
                exact_draw=16, meta_p=32, meta_epi=64, meta_softmax=128,
                unit=256, write_back=512, fused_rmsprop=1024)

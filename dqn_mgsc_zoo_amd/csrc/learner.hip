@@ -4,8 +4,8 @@
 // learned-logit and prioritized samplers, sum trees), the MGSC meta-update
 // and its HVP, Atari preprocessing, the optimizers applied to a finished
 // gradient (Adam, plain RMSProp, global-norm clipping), the categorical (C51)
-// head the learner step launches in place of its own, and the C-ABI entries
-// that drive them.
+// and quantile (QR-DQN) heads the learner step launches in place of its own,
+// and the C-ABI entries that drive them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +23,7 @@
 #include "census.hpp"
 #include "optim.hpp"
 #include "c51.hpp"
+#include "qr.hpp"
 
 using namespace dqz;
 
@@ -1160,6 +1161,306 @@ int dqz_c51_debug_check(int batch, unsigned request) {
   r.slots = iw;
   r.gout = word;
   r.c51 = &head;
+  if (request & DQZ_C51_REQ_WEIGHTS) r.is_weights = word;
+  if (request & DQZ_C51_REQ_PER_DRAW) r.pd = &pd;
+  if (request & DQZ_C51_REQ_UNIFORM_DRAW) r.draw = &draw;
+  if (request & DQZ_C51_REQ_LOGIT_DRAW) r.sm = &sm;
+  if (request & DQZ_C51_REQ_EXACT_DRAW) r.smx = &smx;
+  if (request & DQZ_C51_REQ_META_P) r.meta_p = word;
+  if (request & DQZ_C51_REQ_META_EPI) r.meta_epi = &epi;
+  if (request & DQZ_C51_REQ_META_SOFTMAX) r.meta_sm = &msm;
+  if (request & DQZ_C51_REQ_UNIT) r.unit = 1;
+  if (request & DQZ_C51_REQ_WRITE_BACK) r.wb = &wb;
+  if (request & DQZ_C51_REQ_FUSED_RMSPROP) r.gout = nullptr;
+  return check_step(&L, &P, &S, r);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// the quantile (QR-DQN) agent (qr.hpp)
+
+static_assert(QR_MAX_QUANTILES == QR_MAXN && QR_MAX_OUT == QR_MAXOUT, "learner_impl.hpp restates qr.hpp's limits");
+
+// A dqz_learner on the quantile layout plus the head's own buffers.
+struct dqz_qr {
+  dqz_learner* L;
+  int A, N;
+  QrHead head;  // quantiles and outputs, carved from block
+  void* block;
+};
+static dqz_learner* learner_of(dqz_qr* Q) { return Q ? Q->L : nullptr; }  // null: the shared checks refuse it
+
+static int qr_check_shape(int A, int N) {
+  if (A < 1 || A > MAXA) return fail(DQZ_ERR_INVALID, "num_actions must be in [1, %d]", MAXA);
+  if (N < 1 || N > QR_MAXN) return fail(DQZ_ERR_INVALID, "num_quantiles must be in [1, %d]", QR_MAXN);
+  if (A * N > QR_MAXOUT) return fail(DQZ_ERR_INVALID, "num_actions * num_quantiles must be <= %d", QR_MAXOUT);
+  return DQZ_OK;
+}
+
+static QrHeadArgs qr_head_args(const QrHead& c, int Z, int B, int A) {
+  QrHeadArgs h{};
+  h.out = c.out;
+  h.tau = c.tau;
+  h.kappa = c.kappa;
+  h.Z = Z;
+  h.B = B;
+  h.A = A;
+  h.N = c.N;
+  return h;
+}
+
+int dqz::qr_launch(QrLaunch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const QrHead& c = *r.qr;
+  const int B = L->cfg.batch, A = L->cfg.num_actions, N = c.N;
+  if (which == QR_OUTPUTS) {
+    const NetZ nz{{P->online, P->target, P->online}, {0, 1, 1}};
+    return c51_logits(L, nz, 2, B, A * N, c.out, st);
+  }
+  if (which == QR_HEAD) {
+    QrHeadArgs h = qr_head_args(c, 2, B, A);
+    h.rec = reinterpret_cast<const float4*>(L->rec);
+    h.qv = c.qv;
+    h.theta = c.theta;
+    h.dtheta = c.dtheta;
+    h.dout = c.dout;
+    h.astar = c.astar;
+    h.loss_part = L->loss_part;
+    h.gq = L->gq;
+    h.ga = L->ga;
+    hipLaunchKernelGGL(qr_head_kernel, dim3(B), dim3(QR_THREADS), 0, st, h);
+    DQZ_HIP(hipGetLastError());
+    return DQZ_OK;
+  }
+  if (which == QR_DZ1) {
+    QrDz1Args d{};
+    d.dout = c.dout;
+    d.w2 = P->online + L->off[8];
+    d.h1 = L->h1;
+    d.B = B;
+    d.AN = A * N;
+    d.dz1 = L->dz1;
+    hipLaunchKernelGGL(qr_dz1_kernel, dim3(HID / QR_DZ_ROWS, (B + 15) / 16), dim3(64 * QR_DZ_WAVES), 0, st, d);
+    DQZ_HIP(hipGetLastError());
+    return DQZ_OK;
+  }
+  QrGradArgs g{};
+  g.h1 = L->h1;
+  g.dout = c.dout;
+  g.B = B;
+  g.AN = A * N;
+  g.gw = r.gout + L->off[8];
+  g.gb = r.gout + L->off[9];
+  g.acc = r.gacc;
+  const dim3 grid(HID / 16 + 1, (A * N + 64 * QR_FG_TILES - 1) / (64 * QR_FG_TILES));
+  hipLaunchKernelGGL(qr_fc2_grad_kernel, grid, dim3(256), 0, st, g);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+// q_values of n states through one copy: the torso, the outputs, the head in forward mode (actor: with a draw)
+static int qr_forward_q(dqz_qr* Q, const float* params, const Conv1Src& src, int which, int n, float* q_out,
+                        const ActorDraw* act, hipStream_t st) {
+  dqz_learner* L = Q->L;
+  if (int rc = forward_torso(L, params, src, which, n, st)) return rc;
+  const NetZ nz{{params, params, params}, {which, which, which}};
+  if (int rc = c51_logits(L, nz, 1, n, Q->A * Q->N, Q->head.out, st)) return rc;
+  QrHeadArgs h = qr_head_args(Q->head, 1, n, Q->A);
+  h.fwd_only = 1;
+  h.qv = q_out;
+  if (act) {
+    h.act_out = act->out;
+    h.eps = act->eps;
+    h.act_seed = act->seed;
+    h.act_ctr = act->counter;
+  }
+  hipLaunchKernelGGL(qr_head_kernel, dim3(n), dim3(QR_THREADS), 0, st, h);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+extern "C" {
+
+int dqz_qr_param_layout(int num_actions, int num_quantiles, int64_t offsets[10], int64_t sizes[10], int64_t* total) {
+  if (int rc = qr_check_shape(num_actions, num_quantiles)) return rc;
+  if (!offsets || !sizes || !total) return fail(DQZ_ERR_INVALID, "null output pointer");
+  qr_param_layout(num_actions, num_quantiles, offsets, sizes, total);
+  return DQZ_OK;
+}
+
+int dqz_qr_optimizer_create(const dqz_optimizer_config* cfg, int num_quantiles, dqz_optimizer** out) {
+  if (!cfg || !out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (int rc = qr_check_shape(cfg->num_actions, num_quantiles)) return rc;
+  if (cfg->shared_bias) return fail(DQZ_ERR_INVALID, "the quantile head has no shared bias");
+  return optimizer_create(cfg, num_quantiles, out);  // the wide layout depends on A * N alone
+}
+
+int dqz_qr_create(const dqz_learner_config* cfg, int num_quantiles, const float* quantiles, float huber_param,
+                  dqz_qr** out) {
+  if (!cfg || !quantiles || !out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (int rc = qr_check_shape(cfg->num_actions, num_quantiles)) return rc;
+  if (cfg->batch < 2 || cfg->batch > MAXB) return fail(DQZ_ERR_INVALID, "batch must be in [2, %d]", MAXB);
+  if (cfg->algo != DQZ_ALGO_DQN) return fail(DQZ_ERR_INVALID, "the quantile head runs on a DQN learner");
+  if (!std::isfinite(huber_param) || !(huber_param > 0.f))
+    return fail(DQZ_ERR_INVALID,
+                "huber_param must be finite and > 0 (huber_param = 0, rlax's plain |delta| branch, is not built); "
+                "got %g", (double)huber_param);
+  // the quantiles, checked on the host (this call may synchronise; the step never does)
+  float tau[QR_MAXN];
+  DQZ_HIP(hipMemcpy(tau, quantiles, sizeof(float) * num_quantiles, hipMemcpyDefault));
+  for (int i = 0; i < num_quantiles; ++i)
+    if (!std::isfinite(tau[i]) || !(tau[i] > 0.f && tau[i] < 1.f))
+      return fail(DQZ_ERR_INVALID, "quantiles must be finite and strictly inside (0, 1) (quantile %d)", i);
+  dqz_learner* L = nullptr;
+  if (int rc = dqz_learner_create(cfg, &L)) return rc;
+  const int A = cfg->num_actions, N = num_quantiles;
+  qr_param_layout(A, N, L->off, L->sz, &L->total);  // leaves 0-7 unchanged; the scalar head's L->q stays unused
+  dqz_qr* Q = new dqz_qr();
+  Q->L = L;
+  Q->A = A;
+  Q->N = N;
+  const int64_t B = cfg->batch;
+  const int64_t n_tau = (N + 63) / 64 * 64, n_out = 2 * B * A * N, n_th = (B * N + 63) / 64 * 64;
+  const int64_t n_do = (B * A * N + QR_PAD + 63) / 64 * 64, n_qv = (2 * B * A + 63) / 64 * 64;
+  const int64_t floats = n_tau + (n_out + 63) / 64 * 64 + 2 * n_th + n_do + n_qv + B;
+  if (hipMalloc(&Q->block, floats * sizeof(float)) != hipSuccess ||
+      hipMemset(Q->block, 0, floats * sizeof(float)) != hipSuccess) {
+    if (Q->block) (void)hipFree(Q->block);
+    (void)dqz_learner_destroy(L);
+    delete Q;
+    return fail(DQZ_ERR_HIP, "hipMalloc of %lld bytes of quantile-head scratch failed", (long long)(floats * 4));
+  }
+  float* p = (float*)Q->block;
+  Q->head.N = N;
+  Q->head.tau = p;
+  Q->head.kappa = huber_param;
+  Q->head.out = p + n_tau;
+  Q->head.theta = Q->head.out + (n_out + 63) / 64 * 64;
+  Q->head.dtheta = Q->head.theta + n_th;
+  Q->head.dout = Q->head.dtheta + n_th;
+  Q->head.qv = Q->head.dout + n_do;
+  Q->head.astar = reinterpret_cast<int32_t*>(Q->head.qv + n_qv);
+  if (hipMemcpy(p, tau, sizeof(float) * N, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)dqz_qr_destroy(Q);
+    return fail(DQZ_ERR_HIP, "copy of the quantiles failed");
+  }
+  *out = Q;
+  return DQZ_OK;
+}
+
+int dqz_qr_destroy(dqz_qr* Q) {
+  if (!Q) return DQZ_OK;
+  if (Q->block) (void)hipFree(Q->block);
+  (void)dqz_learner_destroy(Q->L);
+  delete Q;
+  return DQZ_OK;
+}
+
+int dqz_qr_learner(dqz_qr* Q, dqz_learner** out) {
+  if (!Q || !out) return fail(DQZ_ERR_INVALID, "null argument");
+  *out = Q->L;
+  return DQZ_OK;
+}
+
+int dqz_qr_step(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, dqz_optimizer* o,
+                int32_t* count, void* stream) {
+  if (!Q) return fail(DQZ_ERR_INVALID, "null argument");
+  return step_then_apply(Q->L, P, S, {.slots = slots, .qr = &Q->head}, o, count, Q->N, stream);
+}
+
+int dqz_qr_grad(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
+                void* stream) {
+  if (!Q) return fail(DQZ_ERR_INVALID, "null argument");
+  if (!grad_out) return fail(DQZ_ERR_INVALID, "null grad_out");
+  return step_impl(Q->L, P, S, {.slots = slots, .gout = grad_out, .qr = &Q->head}, stream);
+}
+
+int dqz_qr_profile(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
+                   int iters, float* phase_ms, void* stream) {
+  if (!Q) return fail(DQZ_ERR_INVALID, "null argument");
+  if (!grad_out) return fail(DQZ_ERR_INVALID, "null grad_out");
+  return profile_step(Q->L, P, S, {.slots = slots, .gout = grad_out, .qr = &Q->head}, iters, phase_ms, stream);
+}
+
+int dqz_qr_outputs(dqz_qr* Q, float* theta, float* q_values, float* loss_b, float* loss, int32_t* a_star,
+                   void* stream) {
+  if (!Q) return fail(DQZ_ERR_INVALID, "null argument");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t B = Q->L->cfg.batch;
+  const struct {
+    void* dst;
+    const void* src;
+    int64_t n;
+  } rows[] = {{theta, Q->head.theta, B * Q->N},  {q_values, Q->head.qv, 2 * B * Q->A}, {loss_b, Q->L->loss_part, B},
+              {loss, Q->L->loss, 1},             {a_star, Q->head.astar, B}};
+  for (const auto& r : rows)
+    if (r.dst) DQZ_HIP(hipMemcpyAsync(r.dst, r.src, 4 * r.n, hipMemcpyDeviceToDevice, st));
+  return DQZ_OK;
+}
+
+int dqz_qr_debug(dqz_qr* Q, float* outputs, float* dtheta, void* stream) {
+  if (!Q) return fail(DQZ_ERR_INVALID, "null argument");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t B = Q->L->cfg.batch;
+  if (outputs) DQZ_HIP(hipMemcpyAsync(outputs, Q->head.out, 4 * 2 * B * Q->A * Q->N, hipMemcpyDeviceToDevice, st));
+  if (dtheta) DQZ_HIP(hipMemcpyAsync(dtheta, Q->head.dtheta, 4 * B * Q->N, hipMemcpyDeviceToDevice, st));
+  return DQZ_OK;
+}
+
+int dqz_qr_forward(dqz_qr* Q, const float* params, const uint8_t* states, int n, float* q_out, void* stream) {
+  Conv1Src src;
+  if (int rc = forward_src(learner_of(Q), params, n, {.states = states, .q_out = q_out}, &src)) return rc;
+  return qr_forward_q(Q, params, src, 0, n, q_out, nullptr, (hipStream_t)stream);
+}
+
+int dqz_qr_forward_slots(dqz_qr* Q, const float* params, const dqz_store* S, const int32_t* slots, int n, int which,
+                         float* q_out, void* stream) {
+  Conv1Src src;
+  const ForwardInput in{.from_store = true, .store = S, .slots = slots, .which = which, .q_out = q_out};
+  if (int rc = forward_src(learner_of(Q), params, n, in, &src)) return rc;
+  return qr_forward_q(Q, params, src, which, n, q_out, nullptr, (hipStream_t)stream);
+}
+
+int dqz_qr_act(dqz_qr* Q, const float* params, const uint8_t* states, int n, double epsilon, uint64_t seed,
+               uint64_t counter, dqz_action* out, void* stream) {
+  ActorDraw act{epsilon, seed, counter, out};
+  Conv1Src src;
+  if (int rc = forward_src(learner_of(Q), params, n, {.states = states, .act = &act}, &src)) return rc;
+  return qr_forward_q(Q, params, src, 0, n, Q->head.qv, &act, (hipStream_t)stream);
+}
+
+int dqz_qr_debug_check(int batch, unsigned request) {
+  // as dqz_c51_debug_check: host structures whose pointers are set but never followed; check_step alone runs
+  static float word[4];
+  dqz_learner L{};
+  L.cfg.batch = batch;
+  L.cfg.num_actions = 6;
+  L.cfg.algo = DQZ_ALGO_DQN;
+  const dqz_params P{word, word, word, word};
+  dqz_store S{};
+  S.frames = reinterpret_cast<uint8_t*>(word);
+  S.fidx = reinterpret_cast<int32_t*>(word);
+  S.action = reinterpret_cast<int32_t*>(word);
+  S.reward = S.discount = word;
+  S.capacity = 1;
+  int32_t* iw = reinterpret_cast<int32_t*>(word);
+  UniformDraw draw{};
+  draw.slots_out = iw;
+  SoftmaxDraw sm{};
+  sm.slots_out = iw;
+  SoftmaxDrawExact smx{};
+  smx.slots_out = iw;
+  PerSampleArgs pd{};
+  pd.out_slots = iw;
+  const Rms epi{};
+  const MetaSoftmax msm{};
+  const PerWbArgs wb{};
+  const QrHead head{};
+  StepRequest r{};
+  r.slots = iw;
+  r.gout = word;
+  r.qr = &head;
   if (request & DQZ_C51_REQ_WEIGHTS) r.is_weights = word;
   if (request & DQZ_C51_REQ_PER_DRAW) r.pd = &pd;
   if (request & DQZ_C51_REQ_UNIFORM_DRAW) r.draw = &draw;

@@ -247,6 +247,26 @@ inline void c51_param_layout(int A, int N, int64_t off[10], int64_t sz[10], int6
 }
 enum C51Launch { C51_LOGITS, C51_HEAD, C51_FC2_GRAD };
 
+// The quantile (QR-DQN) head in place of the scalar one (StepRequest::qr; qr.hpp): the categorical head's twin.
+// The parameter layout ends in fc2 leaves N * A wide, quantile-major (column i A + a), the step runs in gradient
+// mode, and the head's four launches, which live in the other code object, are made by qr_launch.
+struct QrHead {
+  int N;             // quantiles per action
+  const float* tau;  // [N] device, each strictly inside (0, 1)
+  float kappa;       // huber_param > 0
+  float* out;        // [2][B][A N] online(s_tm1), target(s_t)
+  float* theta;      // [B][N] online outputs of the taken action
+  float* dtheta;     // [B][N] d loss / d those outputs
+  float* dout;       // [B][A N] the dense cotangent of the online outputs
+  float* qv;         // [2][B][A] q_values
+  int32_t* astar;    // [B] argmax_a q_values of the target copy
+};
+constexpr int QR_MAX_QUANTILES = 256, QR_MAX_OUT = 4096;  // qr.hpp's QR_MAXN / QR_MAXOUT
+inline void qr_param_layout(int A, int N, int64_t off[10], int64_t sz[10], int64_t* total) {
+  param_layout(A * N, 0, off, sz, total);  // leaves 0-7 are any DQN network's; fc2 is [512, N A] + [N A]
+}
+enum QrLaunch { QR_OUTPUTS, QR_HEAD, QR_DZ1, QR_FC2_GRAD };
+
 // What one learner step is asked to do, set by name ({.slots = ..., .gout = ...}).  Everything left out is the
 // plain step: centered RMSProp on P->online / mu / nu over the batch `slots`.
 struct StepRequest {
@@ -272,11 +292,18 @@ struct StepRequest {
   PhaseEvents pe;              // dqz_learner_profile: per-phase timing instead of one pass
   // The categorical head (C51): gradient mode only, batch from `slots`; check_step words what it refuses.
   const C51Head* c51;
+  // The quantile head (QR-DQN): as the categorical one, and never both.
+  const QrHead* qr;
 };
 
 // One of the categorical head's three launches of a learner step (learner.hip): the logits of both copies, the
 // per-sample loss head (batch record from L->rec), the fc2 gradient into gout's fc2 leaves.
 int c51_launch(C51Launch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, void* stream);
+
+// One of the quantile head's four launches of a learner step (learner.hip): the outputs of both copies
+// (c51_logits_kernel), the per-sample loss head (batch record from L->rec; writes the dense cotangent), dz1 as a
+// batched product, the fc2 gradient into gout's fc2 leaves.
+int qr_launch(QrLaunch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, void* stream);
 
 // conv1 .. fc1 forward of one network copy on n states (learner_step.hip's forward_impl, Z = 1): the fc1 split-K
 // partials are left in L->fc1p for a head of the other code object.

@@ -13,7 +13,8 @@
 //     dW partials                                                 bwd.hpp
 //   7 reduce of every cross-sample / split-K gradient + centered RMSProp
 // With StepRequest::c51 the categorical head's launches (c51.hpp, the other
-// code object) stand in for 4, and the fc2 gradient follows 7 in one of its own.
+// code object) stand in for 4, and the fc2 gradient follows 7 in one of its own;
+// StepRequest::qr does the same with the quantile head's (qr.hpp).
 // What a step is asked to do (batch source, gradient mode, PER write-back,
 // MGSC meta mode, the categorical head, profiling) is a StepRequest
 // (learner_impl.hpp), whose fields carry the modes' documentation; the
@@ -219,6 +220,19 @@ int dqz::check_step(const dqz_learner* L, const dqz_params* P, const dqz_store* 
       return fail(DQZ_ERR_INVALID, "the categorical head runs in gradient mode only (no fused centered RMSProp)");
     if (L->cfg.batch == 1) return fail(DQZ_ERR_INVALID, "the categorical head needs batch >= 2");
     if (L->cfg.algo != DQZ_ALGO_DQN) return fail(DQZ_ERR_INVALID, "the categorical head runs on a DQN learner");
+    if (r.qr) return fail(DQZ_ERR_INVALID, "a step takes one head: the categorical or the quantile one, not both");
+  }
+  if (r.qr) {  // the quantile head: the same refusals
+    if (r.is_weights) return fail(DQZ_ERR_INVALID, "the quantile head takes no importance weights");
+    if (r.pd) return fail(DQZ_ERR_INVALID, "the quantile head takes no prioritized draw");
+    if (r.draw || r.sm || r.smx) return fail(DQZ_ERR_INVALID, "the quantile head takes no in-launch batch draw");
+    if (r.meta_p || r.meta_epi || r.meta_sm) return fail(DQZ_ERR_INVALID, "the quantile head takes no MGSC meta mode");
+    if (r.unit) return fail(DQZ_ERR_INVALID, "the quantile head takes no unit-cotangent pass");
+    if (r.wb) return fail(DQZ_ERR_INVALID, "the quantile head takes no PER priority write-back");
+    if (!r.gout)
+      return fail(DQZ_ERR_INVALID, "the quantile head takes no fused centered RMSProp (it runs in gradient mode only)");
+    if (L->cfg.batch == 1) return fail(DQZ_ERR_INVALID, "the quantile head needs batch >= 2");
+    if (L->cfg.algo != DQZ_ALGO_DQN) return fail(DQZ_ERR_INVALID, "the quantile head runs on a DQN learner");
   }
   return DQZ_OK;
 }
@@ -308,6 +322,14 @@ int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, c
     DQZ_PHASE(8, if (int rc = c51_launch(C51_HEAD, L, P, r, st)) return rc);
     DQZ_PHASE(5, hipLaunchKernelGGL(fc1_dx_kernel, dim3(fc1_dx_blocks(B)), dim3(256), 0, st, fb);
               DQZ_HIP(hipGetLastError()));
+  } else if (r.qr) {
+    // the quantile head: the outputs of both copies, the per-sample loss head, then dz1 as a batched product over
+    // the head's dense cotangent (qr.hpp, the other code object; slot 2 is one the other steps leave at 0)
+    DQZ_PHASE(4, if (int rc = qr_launch(QR_OUTPUTS, L, P, r, st)) return rc);
+    DQZ_PHASE(8, if (int rc = qr_launch(QR_HEAD, L, P, r, st)) return rc);
+    DQZ_PHASE(2, if (int rc = qr_launch(QR_DZ1, L, P, r, st)) return rc);
+    DQZ_PHASE(5, hipLaunchKernelGGL(fc1_dx_kernel, dim3(fc1_dx_blocks(B)), dim3(256), 0, st, fb);
+              DQZ_HIP(hipGetLastError()));
   } else if (B == 1 && !pe.on()) {
     // one sample (the MGSC pass at theta', the HVP's unit-cotangent pass):
     // the head and fc1 dX in one launch, every block forming the head itself
@@ -359,7 +381,8 @@ int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, c
                        : (chain ? bwd_bc_kernel<false, true> : bwd_bc_kernel<false, false>);
   DQZ_PHASE(6, hipLaunchKernelGGL(bwd, grid, dim3(256), 0, st, c3b, fb, c2b, c1dw, wbk);
             DQZ_HIP(hipGetLastError()));
-  if (pe.on() && !r.c51) pe.ms[7] = pe.ms[8] = 0.f;
+  const bool wide = r.c51 || r.qr;  // a head of the other code object owns the fc2 leaves
+  if (pe.on() && !wide) pe.ms[7] = pe.ms[8] = 0.f;
 
   UpdArgs u{};
   u.th = P->online;
@@ -384,15 +407,16 @@ int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, c
   u.status = L->sync + sync_of(L).err();
   // the categorical head owns the fc2 leaves (c51_fc2_grad_kernel below): with A = nb2 = 0 the small head
   // leaves are fc1/b alone, update_blocks counts 8 blocks for them and no range of small_grad reaches fc2
-  u.A = r.c51 ? 0 : A;
+  u.A = wide ? 0 : A;
   u.B = B;
-  u.nb2 = r.c51 ? 0 : L->shared_bias ? 1 : A;
+  u.nb2 = wide ? 0 : L->shared_bias ? 1 : A;
   u.rms = rms;
   u.rms.sq_off = 4 * (FLAT / 16);  // meta_rms2 partials: the fc1 dW blocks' first, then the update's
   const unsigned nblk = update_blocks(L->sz, u.A, u.nb2);
   DQZ_PHASE(9, hipLaunchKernelGGL(update_kernel, dim3(nblk), dim3(256), 0, st, u);
             DQZ_HIP(hipGetLastError()));
   if (r.c51) DQZ_PHASE(7, if (int rc = c51_launch(C51_FC2_GRAD, L, P, r, st)) return rc);
+  if (r.qr) DQZ_PHASE(7, if (int rc = qr_launch(QR_FC2_GRAD, L, P, r, st)) return rc);
   return DQZ_OK;
 }
 

@@ -654,6 +654,138 @@ class C51Learner(Learner):
   step_uniform = step_logits = step_per_draw = _no_fused_draw
 
 
+def check_huber_param(huber_param):
+  """The quantile head's huber_param as a float; 0 is refused by name."""
+  huber_param = float(huber_param)
+  if huber_param == 0.0:
+    raise NotImplementedError(
+        'huber_param = 0 (rlax\'s plain |delta| branch, whose gradient jumps '
+        'at every delta = 0) is not built: the quantile head takes '
+        'huber_param > 0')
+  if not (np.isfinite(huber_param) and huber_param > 0.0):
+    raise ValueError('huber_param must be finite and > 0')
+  return huber_param
+
+
+class QrLearner(Learner):
+  """The quantile (QR-DQN) learner: `update` of qrdqn/agent.py:112-120 and
+  `select_action` of :122-134 on device (dqz_qr_*).
+
+  Same state surface as `Learner` (params, moments, opt_state, sync_target,
+  sync_status, grad_norm); the step is the learner step with the quantile
+  head, in gradient mode, followed by the optimizer, so the optimizer is Adam
+  or plain RMSProp, alone or behind clip_by_global_norm (the reference's chain,
+  qrdqn/run_atari.py:213-219, is the default)."""
+
+  _qr = None  # dqz_qr handle; it owns the dqz_learner behind _h
+  _OWNER = '_qr'
+  _ENTRIES = dict(destroy='dqz_qr_destroy', forward='dqz_qr_forward',
+                  forward_slots='dqz_qr_forward_slots', act='dqz_qr_act')
+
+  def __init__(self, network: networks_lib.QRNetworkSpec, batch_size,
+               huber_param=1.0, optimizer=None, device='cuda'):
+    if not isinstance(network, networks_lib.QRNetworkSpec):
+      raise ValueError('QrLearner needs networks.qr_atari_network')
+    self.huber_param = check_huber_param(huber_param)
+    optimizer = optimizer or chain(clip_by_global_norm(10.0),
+                                   adam(5e-5, eps=0.01 / 32))
+    if is_centered_rmsprop(optimizer):
+      raise NotImplementedError(
+          'QrLearner applies its optimizer to the finished gradient: centered '
+          'RMSProp exists only fused into the DQN step; use adam(...), '
+          'rmsprop(..., centered=False) or chain(clip_by_global_norm(c), one '
+          'of them)')
+    self.algo = 'qrdqn'
+    self.grad_error_bound = 0.0
+    self._alloc_state(network, batch_size, optimizer, device)
+    b, a, n = self.batch_size, network.num_actions, network.num_quantiles
+    f32 = dict(dtype=torch.float32, device=self.device)
+    self.quantiles = torch.from_numpy(network.quantiles).to(self.device)
+    self.theta = torch.zeros((b, n), **f32)
+    self.q = torch.zeros((2, b, a), **f32)
+    self.loss_b = torch.zeros((b,), **f32)
+    self.loss = torch.zeros((1,), **f32)
+    self.a_star = torch.zeros((b,), dtype=torch.int32, device=self.device)
+    lib = _native.lib()
+    handle = ctypes.c_void_p()
+    _native.check(lib.dqz_qr_create(
+        ctypes.byref(self._learner_config(_native.ALGO_DQN)), n,
+        _native.ptr(self.quantiles), self.huber_param, ctypes.byref(handle)))
+    self._qr = handle
+    inner = ctypes.c_void_p()
+    _native.check(lib.dqz_qr_learner(handle, ctypes.byref(inner)))
+    self._h = inner  # owned by the qr handle: sync_status, fetch_activations
+    self._opt_h = self._create_optimizer(lib.dqz_qr_optimizer_create, n)
+
+  def load_opt_state(self, state):
+    """Restores what opt_state() returned; a centered-RMSProp state (a DQN
+    agent's checkpoint) is refused by name."""
+    if optim_state.is_rmsprop_state(state):
+      raise ValueError(
+          'a centered-RMSProp state cannot restore a QR-DQN learner (its '
+          'optimizer is %s)' % type(self.base_optimizer).__name__)
+    super().load_opt_state(state)
+
+  def step(self, store, slots, stream=None):  # pylint: disable=arguments-differ
+    """One learner step on replay `slots` (device int32 [B])."""
+    self._check_slots(slots)
+    _native.check(_native.lib().dqz_qr_step(
+        self._qr, ctypes.byref(self._params_c), store.c_ref(),
+        _native.ptr(slots), self._opt_h, _native.ptr(self.count),
+        _native.stream_handle(stream)))
+
+  def grad(self, store, slots, out=None, stream=None):  # pylint: disable=arguments-differ
+    """jax.grad(loss_fn) of the same step into a flat tensor (no update)."""
+    self._check_slots(slots)
+    out = torch.zeros_like(self.online) if out is None else out
+    _native.check(_native.lib().dqz_qr_grad(
+        self._qr, ctypes.byref(self._params_c), store.c_ref(),
+        _native.ptr(slots), _native.ptr(out), _native.stream_handle(stream)))
+    return out
+
+  def fetch_outputs(self, stream=None):
+    """(outputs of the taken action theta [B,N], q_values [2,B,A] of
+    online(s_tm1) and target(s_t), per-sample loss [B], mean loss [1], the
+    target's greedy action [B]) of the last step, copied into self tensors."""
+    _native.check(_native.lib().dqz_qr_outputs(
+        self._qr, _native.ptr(self.theta), _native.ptr(self.q),
+        _native.ptr(self.loss_b), _native.ptr(self.loss),
+        _native.ptr(self.a_star), _native.stream_handle(stream)))
+    return self.theta, self.q, self.loss_b, self.loss, self.a_star
+
+  def fetch_head(self, stream=None):
+    """Diagnostic: the last step's q_dist [2,B,N,A] and dtheta [B,N]."""
+    b, a, n = self.batch_size, self.network.num_actions, self.network.num_quantiles
+    q_dist = torch.empty((2, b, n, a), dtype=torch.float32, device=self.device)
+    dtheta = torch.empty((b, n), dtype=torch.float32, device=self.device)
+    _native.check(_native.lib().dqz_qr_debug(
+        self._qr, _native.ptr(q_dist), _native.ptr(dtheta),
+        _native.stream_handle(stream)))
+    return q_dist, dtheta
+
+  def profile(self, store, slots, iters=20, stream=None):  # pylint: disable=arguments-differ
+    """Average ms per launch (dqz_qr_profile), dict; the gradient goes to a
+    scratch tensor and no parameter changes."""
+    self._check_slots(slots)
+    out = (ctypes.c_float * _native.NUM_PHASES)()
+    scratch = torch.zeros_like(self.online)
+    _native.check(_native.lib().dqz_qr_profile(
+        self._qr, ctypes.byref(self._params_c), store.c_ref(),
+        _native.ptr(slots), _native.ptr(scratch), int(iters), out,
+        _native.stream_handle(stream)))
+    names = list(_native.PHASE_NAMES)
+    names[4], names[8], names[2], names[7] = (
+        'qr_outputs', 'qr_head', 'qr_dz1', 'qr_fc2_grad')
+    return {n: float(t) for n, t in zip(names, out) if t > 0.0}
+
+  def _no_fused_draw(self, *unused_args, **unused_kwargs):
+    raise NotImplementedError(
+        'the quantile step takes its batch as slots: sample them first '
+        '(replay.sample_slots) and call step')
+
+  step_uniform = step_logits = step_per_draw = _no_fused_draw
+
+
 class _BorrowedLearner:
   """A dqz_learner the meta handle owns (MetaLearner.debug_learners): what
   Learner.fetch_activations and Learner.fetch_outputs need, nothing else.

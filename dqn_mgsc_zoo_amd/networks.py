@@ -191,3 +191,40 @@ class C51NetworkSpec(NetworkSpec):
 def c51_atari_network(num_actions: int, support) -> C51NetworkSpec:
   """C51 network, expects uint8 input (networks.py:316-335)."""
   return C51NetworkSpec(num_actions, support)
+
+
+class QRNetworkOutputs(typing.NamedTuple):
+  q_values: typing.Any
+  q_dist: typing.Any
+
+
+class QRNetworkSpec(NetworkSpec):
+  """NetworkSpec of the quantile network: `dqn_atari_network`'s leaf names
+  with `linear_1` [512, N * A] wide, plus the fixed `quantiles` (float32 [N],
+  each strictly inside (0, 1)) and their number `num_quantiles`.
+  The layout is quantile-major (`reshape(-1, num_quantiles, num_actions)`):
+  q_dist[b, i, a] = out[b, i * A + a]; q_values[b, a] = mean_i q_dist[b, i, a]."""
+
+  def __new__(cls, num_actions, quantiles):
+    quantiles = np.asarray(quantiles, dtype=np.float32).reshape(-1)
+    if quantiles.size < 1:
+      raise ValueError('num_quantiles < 1: the head needs at least one quantile')
+    if not (np.all(np.isfinite(quantiles)) and np.all(quantiles > 0)
+            and np.all(quantiles < 1)):
+      raise ValueError('quantiles must be finite and strictly inside (0, 1)')
+    self = super().__new__(cls, int(num_actions), False)
+    self.quantiles = quantiles
+    self.num_quantiles = int(quantiles.size)
+    return self
+
+  def leaf_shapes(self):
+    outputs = self.num_actions * self.num_quantiles
+    return [shape_fn(outputs) for _, _, shape_fn, _ in _LEAVES]
+
+  def layout(self):
+    return _native.qr_param_layout(self.num_actions, self.num_quantiles)
+
+
+def qr_atari_network(num_actions: int, quantiles) -> QRNetworkSpec:
+  """QR-DQN network, expects uint8 input (networks.py:295-313)."""
+  return QRNetworkSpec(num_actions, quantiles)

@@ -743,6 +743,90 @@ int dqz_c51_act(dqz_c51* c51, const float* params, const uint8_t* states, int n,
 #define DQZ_C51_REQ_FUSED_RMSPROP 1024u /* no gradient output: the fused centered RMSProp */
 int dqz_c51_debug_check(int batch, unsigned request);
 
+/* ---- the quantile (QR-DQN) agent (qrdqn/agent.py:36-39,88-134) ------------
+ * networks.qr_atari_network (networks.py:295-313): the NatureQNetwork torso
+ * with a last layer N * A wide, N quantile values per action, quantile-major:
+ *   q_dist[b, i, a] = out[b, i A + a];  q_values[b, a] = mean_i q_dist[b, i, a].
+ * Loss (rlax 0.1.2 quantile_q_learning with dist_q_t_selector = dist_q_t: no
+ * double-Q), per sample, x_o = online(s_tm1), x_t = target(s_t):
+ *   a* = argmax_a mean_j x_t[j, a] (first maximum), theta_i = x_o[i, a_b],
+ *   t_j = r + d x_t[j, a*], delta_ij = t_j - theta_i,
+ *   w_ij = |tau_i - 1[delta_ij < 0]|,
+ *   H_k(x) = 0.5 min(|x|, k)^2 + k (|x| - min(|x|, k)),
+ *   loss_b = sum_i (1/N) sum_j w_ij H_k(delta_ij);
+ * the step's loss is the batch mean, and
+ *   d loss / d x_o[b, i, a_b] = -(1 / (N B)) sum_j w_ij clip(delta_ij, -k, k).
+ * k = huber_param > 0 only: huber_param = 0 (rlax's plain |delta| branch) is
+ * refused.  No clip_gradient, no importance weights.
+ * The parameter layout is dqz_param_layout's with leaves 8 and 9 widened:
+ *   8 linear_1/w [512, N A]   9 linear_1/b [N A]
+ * 1 <= N <= 256 and A N <= 4096 (18 actions x 201 quantiles = 3618 fit). */
+int dqz_qr_param_layout(int num_actions, int num_quantiles, int64_t offsets[DQZ_NUM_LEAVES],
+                        int64_t sizes[DQZ_NUM_LEAVES], int64_t* total);
+
+/* dqz_optimizer_create for that layout (cfg->num_actions = A, shared_bias 0). */
+int dqz_qr_optimizer_create(const dqz_optimizer_config* cfg, int num_quantiles, dqz_optimizer** out);
+
+typedef struct dqz_qr dqz_qr;
+
+/* A learner on the quantile layout plus the head's buffers.  cfg: batch
+ * 2..256, num_actions, algo DQZ_ALGO_DQN; its optimizer fields and
+ * grad_error_bound are unused.  quantiles: device f32 [num_quantiles], copied
+ * and checked on the host (this call synchronises): each finite and strictly
+ * inside (0, 1), huber_param finite and > 0; a refusal names the index. */
+int dqz_qr_create(const dqz_learner_config* cfg, int num_quantiles, const float* quantiles, float huber_param,
+                  dqz_qr** out);
+int dqz_qr_destroy(dqz_qr* qr);
+
+/* The dqz_learner inside (owned by the handle): dqz_learner_sync_status and
+ * dqz_learner_debug_activations apply to it; its q stays unused. */
+int dqz_qr_learner(dqz_qr* qr, dqz_learner** out);
+
+/* One jitted `update` (qrdqn/agent.py:112-120): the learner step's forward
+ * with the quantile head in place of the scalar one, its backward in gradient
+ * mode into the optimizer's scratch, the fc2 gradient, then
+ * dqz_optimizer_apply on params->online / mu / nu and `count`.  slots: device
+ * int32 [B].  Same stream, no allocation, no host synchronisation, capturable
+ * in a graph.  The learner's health word keeps its meaning. */
+int dqz_qr_step(dqz_qr* qr, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                dqz_optimizer* opt, int32_t* count, void* stream);
+
+/* Gradient only (jax.grad(loss_fn)) into grad_out, dqz_qr_param_layout order,
+ * padding untouched; mu / nu may be NULL. */
+int dqz_qr_grad(dqz_qr* qr, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                float* grad_out, void* stream);
+
+/* Device-to-device copies of the last step's outputs (any may be NULL):
+ * theta [B][N] online outputs of the taken action, q_values [2][B][A] (online
+ * at s_tm1, target at s_t), loss_b [B] per-sample loss, loss [1] their mean,
+ * a_star int32 [B] the target's greedy action. */
+int dqz_qr_outputs(dqz_qr* qr, float* theta, float* q_values, float* loss_b, float* loss, int32_t* a_star,
+                   void* stream);
+
+/* Diagnostic (tests): the last step's full outputs [2][B][N][A] and
+ * dtheta [B][N] (either may be NULL). */
+int dqz_qr_debug(dqz_qr* qr, float* outputs, float* dtheta, void* stream);
+
+/* dqz_learner_profile of the quantile step (gradient mode into grad_out):
+ * phases 0, 3, 5, 6, 9 as there (9 without the fc2 leaves), 4 the outputs
+ * launch, 8 the per-sample loss head, 2 the batched dz1 product, 7 the fc2
+ * gradient. */
+int dqz_qr_profile(dqz_qr* qr, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                   float* grad_out, int iters, float* phase_ms, void* stream);
+
+/* q_values [n][A] of uint8 states / replay slots, and select_action
+ * (qrdqn/agent.py:122-134): dqz_forward, dqz_forward_slots and dqz_act on the
+ * quantile network; out[i].value = max_a q_values. */
+int dqz_qr_forward(dqz_qr* qr, const float* params, const uint8_t* states, int n, float* q_out, void* stream);
+int dqz_qr_forward_slots(dqz_qr* qr, const float* params, const dqz_store* store, const int32_t* slots, int n,
+                         int which, float* q_out, void* stream);
+int dqz_qr_act(dqz_qr* qr, const float* params, const uint8_t* states, int n, double epsilon, uint64_t seed,
+               uint64_t counter, dqz_action* out, void* stream);
+
+/* Diagnostic (tests): dqz_c51_debug_check for a quantile request; `request`
+ * takes the DQZ_C51_REQ_* bits.  No device call. */
+int dqz_qr_debug_check(int batch, unsigned request);
+
 /* PrioritizedTransitionReplay.add on device (replay.py:1068-1096 ->
  * PrioritizedDistribution.remove_priorities / add_priorities, :642-678): the
  * evicted tree index remove_index (-1: none) is set to 0, add_index to
