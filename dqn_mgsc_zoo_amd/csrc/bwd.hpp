@@ -417,7 +417,7 @@ __device__ __forceinline__ void conv2_bwd_dx(const Conv2BwdArgs& a, float* s_win
   }
   const float4* src = reinterpret_cast<const float4*>(a.dy2 + (int64_t)b * (C2M * C2CO));
   constexpr int NW4 = 121 * 16;  // 1936
-  if constexpr (WAIT) a.sync.wait(b);
+  if constexpr (WAIT) a.sync.wait(b, kTraceDy2);
   float4 r[8];
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
@@ -433,6 +433,7 @@ __device__ __forceinline__ void conv2_bwd_dx(const Conv2BwdArgs& a, float* s_win
     r[q] = in ? v : make_float4(0.f, 0.f, 0.f, 0.f);
   }
   __builtin_amdgcn_sched_barrier(0);  // every window load in flight before the first LDS store
+  if constexpr (WAIT) DQZ_STAMP(kTraceDy2, 2);
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     const int i = t + 256 * q;
@@ -446,6 +447,8 @@ __device__ __forceinline__ void conv2_bwd_dx(const Conv2BwdArgs& a, float* s_win
     }
   }
   __syncthreads();
+  int ack = 0;  // the dy2 acknowledgement flies under the MFMA loop (common.hpp Handoff)
+  if constexpr (WAIT) ack = a.sync.release_issue(b);
   DQZ_STAMP(7, 1);
   // 100 pixels = 6 MFMA row tiles + pixels 96..99 on the VALU (fwd.hpp's trim)
   constexpr int MT = 6;
@@ -478,6 +481,7 @@ __device__ __forceinline__ void conv2_bwd_dx(const Conv2BwdArgs& a, float* s_win
       last[e] += __shfl_xor(last[e], 32, 64);
     }
   }
+  if constexpr (WAIT && !PUB) a.sync.release_finish(b, ack, kTraceDy2);
   __syncthreads();
   DQZ_STAMP(7, 2);
   float* s_red = s_win;  // [4][112][16]
@@ -514,6 +518,7 @@ __device__ __forceinline__ void conv2_bwd_dx(const Conv2BwdArgs& a, float* s_win
     }
   }
   if constexpr (PUB) a.sync1.arrive(b);
+  if constexpr (WAIT && PUB) a.sync.release_finish(b, ack, kTraceDy2);
 }
 
 // conv2 dW as 8 jobs per sample for the merged backward launch: job (kh, ch)
@@ -562,7 +567,7 @@ __device__ __forceinline__ void conv2_bwd_dw_split(const Conv2BwdArgs& a, float*
       *reinterpret_cast<float4*>(s_win + oh * C2W_RS + iw * C2W_S + (rem & 7) * 4) = r[q];
     }
   }
-  a.sync.wait(b);
+  a.sync.wait(b, kTraceDy2);
   float dr[21][2];
 #pragma unroll
   for (int kk = 0; kk < 21; ++kk) {
@@ -574,7 +579,9 @@ __device__ __forceinline__ void conv2_bwd_dw_split(const Conv2BwdArgs& a, float*
       dr[kk][ct] = p < C2M ? v : 0.f;
     }
   }
+  DQZ_STAMP(kTraceDy2, 2);
   __syncthreads();
+  const int ack = a.sync.release_issue(b);  // in flight under the MFMA loop (common.hpp Handoff)
   DQZ_STAMP(13, 1);
   // A = dy2 (rows: co), B = y1 (columns: ci): a lane's accumulators are four
   // consecutive co, stored as one float4 (same bits as the transposed form)
@@ -586,6 +593,7 @@ __device__ __forceinline__ void conv2_bwd_dw_split(const Conv2BwdArgs& a, float*
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct) acc[mt][ct] = mfma4(dr[kk][ct], av, acc[mt][ct]);
     }
+  a.sync.release_finish(b, ack, kTraceDy2);
   float sb[2] = {0.f, 0.f};
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct)

@@ -203,7 +203,7 @@ struct Rms {
 // every workgroup records s_memrealtime (100 MHz, chip-wide) at named points;
 // tools/trace_step.py reads them back with dqz_debug_trace().
 #ifdef DQZ_TRACE
-constexpr int TRACE_KERNELS = 20, TRACE_BLOCKS = 4096, TRACE_SLOTS = 4;
+constexpr int TRACE_KERNELS = 24, TRACE_BLOCKS = 4096, TRACE_SLOTS = 4;
 static __device__ unsigned long long g_dqz_trace[TRACE_KERNELS * TRACE_BLOCKS * TRACE_SLOTS];
 #define DQZ_STAMP(kid, slot)                                                                              \
   do {                                                                                                    \
@@ -318,10 +318,30 @@ inline dim3 xcd_grid(int J, int nsamp) { return dim3((unsigned)(J * ((nsamp + 7)
 // at the workgroup barrier, and one lane adds to the sample's counter
 // (agent-scope atomic); one consumer lane polls the counter with sc1 loads,
 // the workgroup barrier releases the other waves, and every payload load is
-// an sc1 load.  The last of `consumers` consumers to pass resets the
-// sample's words, so every launch starts from zero (the learner scratch is
-// zeroed at creation).  A spin that outlives ~2^24 polls sets *err and gives
-// up rather than hang the GPU.
+// an sc1 load.  A spin that outlives ~2^24 polls sets *err and gives up
+// rather than hang the GPU.
+//
+// The acknowledgement is apart from the wait.  wait() is the poll and the
+// barrier only, so the window loads follow "the data is there" at once.
+// Every consumer then counts itself on the sample's ack word and the last of
+// `consumers` to do so resets the sample's two words for the next launch;
+// nothing in the current launch reads them again, so the returning atomic is
+// taken off the chain: release_issue() (after the barrier behind the LDS
+// staging of the window: the atomic flies under the MFMA loop) hands its
+// result to release_finish() (after the MFMA loop, or after arrive() in a
+// body that publishes: compare, and the two reset stores).  Invariants:
+//   * every block that called wait() releases exactly once on every path,
+//     the give-up path included (the bodies are straight-line code);
+//   * `consumers` counts exactly those blocks (dy2: the conv2 dX and the
+//     conv2 dW jobs of the sample);
+//   * the last release happens inside the launch, so every cnt / ack word is
+//     zero when the launch ends (graph replays and dqz_learner_profile's
+//     repeated launches start from zero; the scratch is zeroed at creation);
+//   * a block acknowledges only after its own poll has passed, so the reset
+//     cannot overtake a consumer that still polls.
+// wait_release() is the three back to back (the HVP's one wait).
+// hk: the hand-off's trace rows (DQZ_TRACE builds: slot 0 poll passed, 1
+// barrier left, 2 window loads issued, 3 release finished).
 struct Handoff {
   static constexpr int kStride = 64;  // one 256-byte line pair per sample word: pollers of
                                       // different samples never share a line
@@ -335,7 +355,7 @@ struct Handoff {
     __syncthreads();
     if (threadIdx.x == 0) __hip_atomic_fetch_add(cnt + b * kStride, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  __device__ __forceinline__ void wait(int b) const {
+  __device__ __forceinline__ void wait(int b, [[maybe_unused]] int hk = -1) const {
     if (threadIdx.x == 0) {
       unsigned spins = 0;
       while (__hip_atomic_load(cnt + b * kStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
@@ -345,14 +365,45 @@ struct Handoff {
           break;
         }
       }
-      if (__hip_atomic_fetch_add(ack + b * kStride, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == consumers - 1) {
-        __hip_atomic_store(cnt + b * kStride, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(ack + b * kStride, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
     }
+    if (hk >= 0) DQZ_STAMP(hk, 0);
     __syncthreads();
+    if (hk >= 0) DQZ_STAMP(hk, 1);
+  }
+  // The acknowledgement's first half: thread 0 counts the block on the
+  // sample's ack word.  The returned count is not used here, so the atomic's
+  // round trip is not waited for where it is issued.
+  __device__ __forceinline__ int release_issue(int b) const {
+    int prior = 0;
+    // The word's address goes through a lane-dependent zero (lane 0's mbcnt).
+    // With a wave-uniform address the compiler rewrites the atomic for a
+    // whole wave (one lane adds the wave's count, the result is broadcast
+    // with v_readfirstlane) and has to wait for it (vmcnt(0)) on the spot.
+    if (threadIdx.x == 0) {
+      int* p = ack + b * kStride + __builtin_amdgcn_mbcnt_lo(~0u, 0u);
+      prior = __hip_atomic_fetch_add(p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return prior;
+  }
+  // Its second half: the last consumer of the sample resets the two words.
+  __device__ __forceinline__ void release_finish(int b, int prior, [[maybe_unused]] int hk = -1) const {
+    // the compare (and the vmcnt wait in front of it) stays here: left alone
+    // the scheduler hoists it into the MFMA loop the atomic is to fly under
+    __builtin_amdgcn_sched_barrier(0);
+    if (threadIdx.x == 0 && prior == consumers - 1) {
+      __hip_atomic_store(cnt + b * kStride, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(ack + b * kStride, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (hk >= 0) DQZ_STAMP(hk, 3);
+  }
+  __device__ __forceinline__ void wait_release(int b) const {
+    wait(b);
+    release_finish(b, release_issue(b));
   }
 };
+
+// Trace rows of the four hand-offs of the step (Handoff's hk): y1, y2, dy2, dy1.
+constexpr int kTraceY1 = 20, kTraceY2 = 21, kTraceDy2 = 22, kTraceDy1 = 23;
 
 // 16-byte sc1 (L1-bypassing) load of element e of a float4 array of `bytes`
 // bytes whose base is wave-uniform (buffer_load_dwordx4 ... sc1).

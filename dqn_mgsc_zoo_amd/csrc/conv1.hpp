@@ -387,7 +387,7 @@ __device__ __forceinline__ void conv1_dw_body(const Conv1DwArgs& a, float* smem,
     if (tid < 2 * QPC && f >= 0)
       v = reinterpret_cast<const uint4*>(a.src.frames + (int64_t)f * FB + row0 * FW)[pj];
   }
-  a.sync1.wait(b);
+  a.sync1.wait(b, kTraceDy1);
   const float* dyb = a.dy1 + ((int64_t)b * C1M + rb * C1_POS) * C1CO;
   const int co = tid & 31, c0 = tid >> 5;  // this thread: chunks c0 and c0 + 8 of channel co
   float dv[2][8];
@@ -399,6 +399,7 @@ __device__ __forceinline__ void conv1_dw_body(const Conv1DwArgs& a, float* smem,
       dv[it][j] = (c < 15 && ow0 + j < C1O)
                       ? load_sc1_f1(dyb, C1_POS * C1CO * 4, (oh * C1O + ow0 + j) * C1CO + co) : 0.f;
   }
+  DQZ_STAMP(kTraceDy1, 2);
   if (tid < 2 * QPC) store_bytes_as_bf16(s_in + cl * C1_PLANE + pj * 16, v);
 #pragma unroll
   for (int it = 0; it < 2; ++it) {
@@ -423,6 +424,7 @@ __device__ __forceinline__ void conv1_dw_body(const Conv1DwArgs& a, float* smem,
     s_bp[c * C1CO + co] = sb;
   }
   __syncthreads();
+  const int ack = a.sync1.release_issue(b);  // in flight under the MFMA loop (common.hpp Handoff)
   DQZ_STAMP(8, 1);
   const int lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 5, i = lane & 31;
@@ -455,6 +457,7 @@ __device__ __forceinline__ void conv1_dw_body(const Conv1DwArgs& a, float* smem,
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dq, xb, acc, 0, 0, 0);
     }
   }
+  a.sync1.release_finish(b, ack, kTraceDy1);
   // C col = lane & 31 = m -> kh = 2 wave + (m >> 4), kw = (m >> 1) & 7, ci = 2 ch + (m & 1);
   // rows co = (r & 3) + 8 (r >> 2) + 4 h: one float4 store per r >> 2.  The
   // sums are over raw pixels: dW = (sum x dy) / 255 (networks.py:192)

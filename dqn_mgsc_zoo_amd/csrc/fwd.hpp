@@ -86,7 +86,7 @@ __device__ __forceinline__ void conv2_fwd_body(const LayerFwdArgs& a, float* s_i
   for (int kk = 0; kk < 32; ++kk) wr[kk] = W[(w * 128 + 4 * kk + kq) * C2CO + 16 * nq + n];
   const float4* src = reinterpret_cast<const float4*>(a.in + ((int64_t)z * a.B + b) * (C1M * C1CO));
   constexpr int NQ4 = C1M * C1CO / 4;  // 3200
-  if constexpr (WAIT) a.wait.wait(sj.s);
+  if constexpr (WAIT) a.wait.wait(sj.s, kTraceY1);
   float4 r[13];
 #pragma unroll
   for (int q = 0; q < 13; ++q) {
@@ -99,6 +99,7 @@ __device__ __forceinline__ void conv2_fwd_body(const LayerFwdArgs& a, float* s_i
   // scheduler issued the 13th only after ten had returned: one more round
   // trip after the hand-off)
   __builtin_amdgcn_sched_barrier(0);
+  if constexpr (WAIT) DQZ_STAMP(kTraceY1, 2);
 #pragma unroll
   for (int q = 0; q < 13; ++q) {
     const int i = t + 256 * q;
@@ -113,6 +114,8 @@ __device__ __forceinline__ void conv2_fwd_body(const LayerFwdArgs& a, float* s_i
   }
   DQZ_STAMP(1, 1);
   __syncthreads();
+  int ack = 0;  // the y1 acknowledgement flies under the MFMA loop (common.hpp Handoff)
+  if constexpr (WAIT) ack = a.wait.release_issue(sj.s);
   // 81 positions = 5 MFMA row tiles + position 80, which every lane folds
   // from its own weight registers on the VALU (a 6th tile would be 1/16 live)
   constexpr int MT = 5;
@@ -135,6 +138,7 @@ __device__ __forceinline__ void conv2_fwd_body(const LayerFwdArgs& a, float* s_i
     last = __fmaf_rn(s_in[blast + off], wr[kk], last);
   }
   DQZ_STAMP(1, 2);
+  if constexpr (WAIT && !PUB) a.wait.release_finish(sj.s, ack, kTraceY1);
   {
     last += __shfl_xor(last, 16, 64);
     last += __shfl_xor(last, 32, 64);
@@ -172,6 +176,7 @@ __device__ __forceinline__ void conv2_fwd_body(const LayerFwdArgs& a, float* s_i
       store_sc1_f4(out, (C2M * C2CO - 16 * nq) * 4, 4 * (p * C2CO + c4), f32x4{o[0], o[1], o[2], o[3]});
     }
     a.pub.arrive(sj.s);
+    if constexpr (WAIT) a.wait.release_finish(sj.s, ack, kTraceY1);
   } else {
     for (int i = t; i < C2M * 16; i += 256) {
       const int k = red_idx(i >> 4, i & 15);
@@ -214,12 +219,13 @@ __device__ __forceinline__ void conv2_fwd8_body(const LayerFwdArgs& a, float* s_
   const float4* src = reinterpret_cast<const float4*>(a.in + ((int64_t)z * a.B + b) * (C1M * C1CO)) +
                       ih0 * C1O * (C1CO / 4);
   const int nq4 = nrows * C1O * (C1CO / 4);  // 1920 / 1600 float4
-  a.wait.wait(sj.s);
+  a.wait.wait(sj.s, kTraceY1);
   constexpr int NL = (2 * C2F_ROWS0 + 2) * C1O * (C1CO / 4) / 256;  // 7.5 -> 8 loads per thread at most
   float4 r[NL + 1];
 #pragma unroll
   for (int q = 0; q <= NL; ++q) r[q] = load_sc1_f4(src, nq4 * 16, min(t + 256 * q, nq4 - 1));
   __builtin_amdgcn_sched_barrier(0);  // every window load in flight before the first LDS store
+  DQZ_STAMP(kTraceY1, 2);
 #pragma unroll
   for (int q = 0; q <= NL; ++q) {
     const int i = t + 256 * q;
@@ -234,6 +240,7 @@ __device__ __forceinline__ void conv2_fwd8_body(const LayerFwdArgs& a, float* s_
   }
   DQZ_STAMP(1, 1);
   __syncthreads();
+  const int ack = a.wait.release_issue(sj.s);  // in flight under the MFMA loop
   constexpr int MT = 3;  // 48 rows: the tail rows clamp to the last position and are not stored
   int base[MT];
 #pragma unroll
@@ -277,6 +284,7 @@ __device__ __forceinline__ void conv2_fwd8_body(const LayerFwdArgs& a, float* s_
     store_sc1_f4(out, out_bytes, 4 * (p * C2CO + c4), f32x4{o[0], o[1], o[2], o[3]});
   }
   a.pub.arrive(sj.s);
+  a.wait.release_finish(sj.s, ack, kTraceY1);
   DQZ_STAMP(1, 3);
 }
 
@@ -300,7 +308,7 @@ __device__ __forceinline__ void conv3_fwd_body(const LayerFwdArgs& a, float* s_i
     wr[kk] = W[((kk >> 2) * C3CI + 16 * w + 4 * (kk & 3) + kq) * C3CO + 16 * nq + n];
   const float4* src = reinterpret_cast<const float4*>(a.in + ((int64_t)z * a.B + b) * (C2M * C2CO));
   constexpr int NQ4 = C2M * C2CO / 4;  // 1296
-  if constexpr (WAIT) a.wait.wait(sj.s);
+  if constexpr (WAIT) a.wait.wait(sj.s, kTraceY2);
   float4 r[6];
 #pragma unroll
   for (int q = 0; q < 6; ++q) {
@@ -310,6 +318,7 @@ __device__ __forceinline__ void conv3_fwd_body(const LayerFwdArgs& a, float* s_i
       r[q] = src[min(t + 256 * q, NQ4 - 1)];
   }
   __builtin_amdgcn_sched_barrier(0);  // every window load in flight before the first LDS store
+  if constexpr (WAIT) DQZ_STAMP(kTraceY2, 2);
 #pragma unroll
   for (int q = 0; q < 6; ++q) {
     const int i = t + 256 * q;
@@ -324,6 +333,8 @@ __device__ __forceinline__ void conv3_fwd_body(const LayerFwdArgs& a, float* s_i
   }
   DQZ_STAMP(2, 1);
   __syncthreads();
+  int ack = 0;  // the y2 acknowledgement flies under the MFMA loop (common.hpp Handoff)
+  if constexpr (WAIT) ack = a.wait.release_issue(sj.s);
   // 49 positions = 3 MFMA row tiles + position 48 on the VALU (see conv2)
   constexpr int MT = 3;
   int base[MT];
@@ -346,6 +357,7 @@ __device__ __forceinline__ void conv3_fwd_body(const LayerFwdArgs& a, float* s_i
     last = __fmaf_rn(s_in[blast + off], wr[kk], last);
   }
   DQZ_STAMP(2, 2);
+  if constexpr (WAIT) a.wait.release_finish(sj.s, ack, kTraceY2);
   {
     last += __shfl_xor(last, 16, 64);
     last += __shfl_xor(last, 32, 64);
@@ -410,12 +422,13 @@ __device__ __forceinline__ void conv3_fwd8_body(const LayerFwdArgs& a, float* s_
   const float4* src = reinterpret_cast<const float4*>(a.in + ((int64_t)z * a.B + b) * (C2M * C2CO)) +
                       oh0 * C2O * (C2CO / 4);
   const int nq4 = nrows * C2O * (C2CO / 4);  // 864 / 720 float4
-  a.wait.wait(sj.s);
+  a.wait.wait(sj.s, kTraceY2);
   constexpr int NL = ((C3F_ROWS0 + C3K - 1) * C2O * (C2CO / 4) + 255) / 256;  // 4
   float4 r[NL];
 #pragma unroll
   for (int q = 0; q < NL; ++q) r[q] = load_sc1_f4(src, nq4 * 16, min(t + 256 * q, nq4 - 1));
   __builtin_amdgcn_sched_barrier(0);  // every window load in flight before the first LDS store
+  DQZ_STAMP(kTraceY2, 2);
 #pragma unroll
   for (int q = 0; q < NL; ++q) {
     const int i = t + 256 * q;
@@ -430,6 +443,7 @@ __device__ __forceinline__ void conv3_fwd8_body(const LayerFwdArgs& a, float* s_
   }
   DQZ_STAMP(2, 1);
   __syncthreads();
+  const int ack = a.wait.release_issue(sj.s);  // in flight under the MFMA loop
   constexpr int MT = 2;  // 32 rows: the tail rows clamp to the last position and are not stored
   int base[MT];
 #pragma unroll
@@ -448,6 +462,7 @@ __device__ __forceinline__ void conv3_fwd8_body(const LayerFwdArgs& a, float* s_
     for (int m = 0; m < MT; ++m) acc[m] = mfma4(s_in[base[m] + off], wr[kk], acc[m]);
   }
   DQZ_STAMP(2, 2);
+  a.wait.release_finish(sj.s, ack, kTraceY2);
   __syncthreads();
   float* s_red = s_in;  // [4][32 rows, padded][16]
   constexpr int RW = red_rows(16 * MT);

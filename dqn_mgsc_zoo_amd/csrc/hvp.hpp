@@ -685,7 +685,7 @@ __device__ __forceinline__ void hvp_g_conv1(const HvpArgs& a, int k, float (*s_r
     for (int p = t; p < C1M; p += 256) s_x[p] = 1.f;  // bias row: sum_p ddot1
   }
   DQZ_STAMP(18, 1);
-  a.td1_pub.wait(0);  // its barrier also publishes s_x
+  a.td1_pub.wait_release(0);  // its barrier also publishes s_x
   DQZ_STAMP(18, 2);
   float tv[50];       // this thread's ddot1 column
 #pragma unroll

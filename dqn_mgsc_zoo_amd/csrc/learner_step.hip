@@ -500,6 +500,18 @@ int dqz_learner_debug_backward(dqz_learner* L, int chain, int* active) {
   return DQZ_OK;
 }
 
+int dqz_learner_debug_sync_words(dqz_learner* L, int32_t* out, int64_t n, int64_t* total) {
+  if (!L) return fail(DQZ_ERR_INVALID, "null learner");
+  const int64_t ints = sync_of(L).ints();
+  if (total) *total = ints;
+  if (n < 0 || n > ints) return fail(DQZ_ERR_INVALID, "n must be in [0, %lld]", (long long)ints);
+  if (n > 0 && !out) return fail(DQZ_ERR_INVALID, "null out");
+  if (n == 0) return DQZ_OK;
+  DQZ_HIP(hipDeviceSynchronize());
+  DQZ_HIP(hipMemcpy(out, L->sync, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  return DQZ_OK;
+}
+
 int dqz_learner_outputs(dqz_learner* L, float* q_tm1, float* td, float* loss, void* stream) {
   if (!L) return fail(DQZ_ERR_INVALID, "null learner");
   hipStream_t st = (hipStream_t)stream;

@@ -429,6 +429,17 @@ class Learner:
         self._h, int(chain), ctypes.byref(active)))
     return active.value
 
+  def debug_sync_words(self):
+    """Test hook (dqz_learner_debug_sync_words): the learner's in-launch
+    hand-off words and error word as a numpy int32 array (synchronises).
+    All zero between launches."""
+    total = ctypes.c_int64(0)
+    fn = _native.lib().dqz_learner_debug_sync_words
+    _native.check(fn(self._h, None, 0, ctypes.byref(total)))
+    out = np.zeros((total.value,), np.int32)
+    _native.check(fn(self._h, out.ctypes.data, total.value, None))
+    return out
+
   def fetch_activations(self, z=0, backward=False, stream=None):
     """Diagnostic (dqz_learner_debug_activations): the intermediates of the
     most recent step / gradient call as a dict of fresh device tensors.

@@ -248,6 +248,15 @@ int dqz_learner_debug_stall(dqz_learner* learner, int sample, unsigned spin_max)
  * captured with. */
 int dqz_learner_debug_backward(dqz_learner* learner, int chain, int* active);
 
+/* Diagnostic (tests): the learner's in-launch hand-off words, read back.
+ * *total (may be NULL) returns how many ints the learner keeps: the arrival
+ * and acknowledgement words of every hand-off (64 ints apart) and the error
+ * word of dqz_learner_sync_status.  With n > 0 the device is synchronised
+ * and the first n <= *total ints are copied to the host array `out`; n = 0
+ * only reports *total.  Between launches every int is zero (a wait that gave
+ * up leaves the error word set until dqz_learner_sync_status reads it). */
+int dqz_learner_debug_sync_words(dqz_learner* learner, int32_t* out, int64_t n, int64_t* total);
+
 /* Diagnostic (tests): device-to-device copies of the intermediates the
  * learner's scratch holds after its most recent learner step, gradient call
  * or forward (any output may be NULL; no kernel is launched; the copies are

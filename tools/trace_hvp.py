@@ -23,7 +23,7 @@ import torch  # noqa: E402
 from dqn_mgsc_zoo_amd import _native, learner as learner_lib, networks, replay as replay_lib, synthetic  # noqa: E402
 from dqn_mgsc_zoo_amd import replay_circular as rc  # noqa: E402
 
-K, NB, NS = 20, 4096, 4  # common.hpp TRACE_*
+K, NB, NS = 24, 4096, 4  # common.hpp TRACE_*
 B, A, M = 32, 6, 100
 # block ranges per launch (hvp.hpp): name, first block
 RANGES = {

@@ -31,7 +31,7 @@ from dqn_mgsc_zoo_amd import _native, learner as learner_lib, networks, syntheti
 NAMES = {10: 'sample', 0: 'conv1_fwd', 1: 'conv2_fwd', 2: 'conv3_fwd', 3: 'fc1_fwd', 4: 'head', 5: 'fc1_dx',
          6: 'conv3_dx', 7: 'conv2_dx', 8: 'conv1_dw', 9: 'update', 11: 'fc1_dw*', 12: 'conv3_dw*', 13: 'conv2_dw*', 14: 'c1_stage*', 15: 'head_sub*'}
 ORDER = [10, 0, 14, 1, 2, 3, 4, 15, 5, 6, 11, 7, 12, 8, 13, 9]
-K, NB, NS = 20, 4096, 4  # common.hpp TRACE_*: kernels 16-18 are the HVP launches (tools/trace_hvp.py)
+K, NB, NS = 24, 4096, 4  # common.hpp TRACE_*: kernels 16-18 are the HVP launches (tools/trace_hvp.py)
 
 dev = torch.device('cuda:0')
 cap = int(os.environ.get('CAP', '200000'))
@@ -129,3 +129,20 @@ for k in ORDER:
             (np.percentile(e, 90) - t0) / 100, (e.max() - t0) / 100, np.median(e - b0) / 100))
   if not NAMES[k].endswith('*'):
     prev_end = end
+# The in-launch hand-offs (common.hpp Handoff, rows kTraceY1 .. kTraceDy1), per consumer block: slot 0 poll passed,
+# 1 barrier left, 2 window loads issued, 3 release finished (compare done, reset stores issued).  `mfma->rel` is from
+# the end of the consumer stage's MFMA loop (its slot 2, where it has one) to slot 3: what the finish half waited.
+HANDS = [(20, 'y1', 1, 'conv2_fwd'), (21, 'y2', 2, 'conv3_fwd'), (22, 'dy2', 7, 'conv2_dx'), (22, 'dy2', 13, 'conv2_dw'),
+         (23, 'dy1', 8, 'conv1_dw')]
+print('%-6s %-10s %8s %8s %8s %8s %8s %8s' % ('word', 'consumer', 'poll->bar', 'bar->ld', 'poll->ld', 'ld->rel',
+                                               'mfma->rel', 'nblk'))
+for k, word, stage, name in HANDS:
+  ok = (t[k, :, 0] > 0) & (t[k, :, 2] > 0) & (t[k, :, 3] > 0) & (t[stage, :, 1] > 0)
+  if not ok.any():
+    continue
+  d = lambda a, b: np.median(a[ok] - b[ok]) / 100
+  m2 = ok & (t[stage, :, 2] > 0)
+  tail = np.median(t[k, m2, 3] - t[stage, m2, 2]) / 100 if m2.any() else float('nan')
+  print('%-6s %-10s %8.2f %8.2f %8.2f %8.2f %8.2f %8d' % (
+      word, name, d(t[k, :, 1], t[k, :, 0]), d(t[k, :, 2], t[k, :, 1]), d(t[k, :, 2], t[k, :, 0]),
+      d(t[k, :, 3], t[k, :, 2]), tail, ok.sum()))
