@@ -529,8 +529,41 @@ __device__ __forceinline__ void conv2_bwd_dx(const Conv2BwdArgs& a, float* s_win
 // dy2 comes from this launch's conv3 dX jobs (wait + sc1 loads).
 constexpr int C2V_WIN = 9 * C2W_RS;  // 7272 floats
 
+// A lane's read of a lane of its own quad (every lane has a source: no "old" value)
+template <int CTRL>
+__device__ __forceinline__ float quad_perm_f(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+
+// 4 x 4 transpose inside each quad of lanes (DPP quad permutes, no LDS): lane
+// e of a quad comes with row e in v and leaves with column e, v[j] = lane j's
+// v[e].  Two butterfly steps: 2 x 2 blocks over (lane bit 0, index bit 0)
+// with the xor-1 neighbour, then over bit 1 with the xor-2 neighbour.  The
+// permutes stand outside the selects (inside, the compiler branches on the
+// lane bit around them).
+__device__ __forceinline__ void quad_transpose4(float (&v)[4]) {
+  const bool b0 = threadIdx.x & 1, b1 = threadIdx.x & 2;
+#pragma unroll
+  for (int h = 0; h < 4; h += 2) {
+    const float lo = v[h], hi = v[h + 1];
+    const float plo = quad_perm_f<0xB1>(lo), phi = quad_perm_f<0xB1>(hi);
+    v[h] = b0 ? phi : lo;
+    v[h + 1] = b0 ? hi : plo;
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float lo = v[h], hi = v[h + 2];
+    const float plo = quad_perm_f<0x4E>(lo), phi = quad_perm_f<0x4E>(hi);
+    v[h] = b1 ? phi : lo;
+    v[h + 2] = b1 ? hi : plo;
+  }
+}
+
 // conv2 dW job (sample b, kernel row kh, output-channel half ch): y1 rows to
 // LDS (loaded before the wait), the wait for the sample's dy2, the MFMAs.
+// WIDE (the chain grid): the dy2 window as 16-byte loads and a quad
+// transpose; otherwise one four-byte load per value (the same bits in dr).
+template <bool WIDE>
 __device__ __forceinline__ void conv2_bwd_dw_split(const Conv2BwdArgs& a, float* s_win, int b, int kh, int ch) {
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;  // w = kw
   const int n = lane & 15, kq = lane >> 4;
@@ -568,18 +601,56 @@ __device__ __forceinline__ void conv2_bwd_dw_split(const Conv2BwdArgs& a, float*
     }
   }
   a.sync.wait(b, kTraceDy2);
-  float dr[21][2];
+  float dr[21][2];  // dr[kk][ct] = dy2[b][p = 4 kk + kq][32 ch + 16 ct + n], zero past position 80
+  if constexpr (WIDE) {
+    // 16-byte sc1 loads, as the conv3 dX jobs stored them: lane n = 4 q + e
+    // fetches the four channels 32 ch + 16 ct + 4 q .. + 3 of position
+    // 4 (4 g + e) + kq, g = 0..5 (12 loads instead of 42 four-byte ones), and
+    // the quad's transpose hands lane e its channel n of positions
+    // 4 (4 g + e') + kq, e' = 0..3: dr[4 g + e'][ct]
+    const float4* src = reinterpret_cast<const float4*>(a.dy2 + (int64_t)b * (C2M * C2CO));
+    const int q4 = n >> 2, e = n & 3;
+    float4 ld[6][2];
 #pragma unroll
-  for (int kk = 0; kk < 21; ++kk) {
-    const int p = 4 * kk + kq;
+    for (int g = 0; g < 6; ++g)
 #pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-      const float* gp = a.dy2 + ((int64_t)b * C2M + min(p, C2M - 1)) * C2CO + 32 * ch + 16 * ct + n;
-      const float v = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      dr[kk][ct] = p < C2M ? v : 0.f;
+      for (int ct = 0; ct < 2; ++ct)
+        ld[g][ct] = load_sc1_f4(src, C2M * C2CO * 4,
+                                min(4 * (4 * g + e) + kq, C2M - 1) * (C2CO / 4) + 8 * ch + 4 * ct + q4);
+    __builtin_amdgcn_sched_barrier(0);  // every load in flight before the first transpose
+    DQZ_STAMP(kTraceDy2, 2);
+#pragma unroll
+    for (int g = 0; g < 6; ++g)
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) {
+        float v[4] = {ld[g][ct].x, ld[g][ct].y, ld[g][ct].z, ld[g][ct].w};
+        if (g == 5) {  // positions 80 + 4 e + kq: only 80 exists
+          const bool in = 4 * (4 * g + e) + kq < C2M;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = in ? v[j] : 0.f;
+        }
+        quad_transpose4(v);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (4 * g + j < 21) {
+            asm volatile("" : "+v"(v[j]));  // the selects stay here: sunk, they sit in the MFMA loop
+            dr[4 * g + j][ct] = v[j];
+          }
+        __builtin_amdgcn_sched_barrier(0);  // in load order: each transpose waits for its own load only
+      }
+  } else {
+#pragma unroll
+    for (int kk = 0; kk < 21; ++kk) {
+      const int p = 4 * kk + kq;
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) {
+        const float* gp = a.dy2 + ((int64_t)b * C2M + min(p, C2M - 1)) * C2CO + 32 * ch + 16 * ct + n;
+        const float v = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        dr[kk][ct] = p < C2M ? v : 0.f;
+      }
     }
+    DQZ_STAMP(kTraceDy2, 2);
   }
-  DQZ_STAMP(kTraceDy2, 2);
   __syncthreads();
   const int ack = a.sync.release_issue(b);  // in flight under the MFMA loop (common.hpp Handoff)
   DQZ_STAMP(13, 1);
@@ -928,7 +999,10 @@ __device__ __forceinline__ void bwd_chain_block(const Conv3BwdArgs& c3, const Co
 //
 // CHAIN (legal for at most BWD_CHAIN_MAXB samples and the default for 2 .. BWD_CHAIN_MAXB:
 // learner_impl.hpp bwd_chain_active, dqz_learner_debug_backward):
-//   [chain 8/sample] [fc1 dW 784] [conv3 dW 4/sample] [conv2 dW 8/sample]
+//   [chain 8/sample] [fc1 dW 784] [conv2 dW 8/sample] [conv3 dW 4/sample]
+// (conv2 dW, with its dy2 window as 16-byte loads, ahead of conv3 dW: +1 %
+// together, neither alone, so the grid below keeps its loads and its order;
+// DESIGN §4 "Round 9").
 // A chain block carries job j of its sample through conv3 dX, conv2 dX and
 // conv1 dW (bwd_chain_block above), so the dX chain never waits for a
 // dispatch.  Termination: the chain blocks have the lowest indices and
@@ -1021,6 +1095,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     }
     i -= 8 * B8;
   }
+  if constexpr (CHAIN) {
+    // conv2 dW (which waits for dy2) ahead of conv3 dW (which waits for nothing)
+    if (i < 8 * B8) {
+      const SampleJob sj = xcd_sample_job_at(i, 8, c2.B);
+      if (!sj.valid) return;
+      DQZ_STAMP(13, 0);
+      conv2_bwd_dw_split<true>(c2, smem, sj.s, sj.job >> 1, sj.job & 1);
+      DQZ_STAMP(13, 3);
+      return;
+    }
+    i -= 8 * B8;
+    const SampleJob sj = xcd_sample_job_at(i, 4, c3.B);
+    if (!sj.valid) return;
+    DQZ_STAMP(12, 0);
+    conv3_bwd_dw(c3, smem, sj.s, sj.job);
+    DQZ_STAMP(12, 3);
+    return;
+  }
   if (i < 4 * B8) {
     const SampleJob sj = xcd_sample_job_at(i, 4, c3.B);
     if (!sj.valid) return;
@@ -1046,7 +1138,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   const SampleJob sj = xcd_sample_job_at(i, 8, c2.B);
   if (!sj.valid) return;
   DQZ_STAMP(13, 0);
-  conv2_bwd_dw_split(c2, smem, sj.s, sj.job >> 1, sj.job & 1);
+  conv2_bwd_dw_split<false>(c2, smem, sj.s, sj.job >> 1, sj.job & 1);
   DQZ_STAMP(13, 3);
 }
 
