@@ -246,72 +246,6 @@ SIGNATURES = {
         _int,
         [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore),
          ctypes.POINTER(DqzPerDraw), _vp, _vp, _vp]),
-    'dqz_c51_param_layout': (
-        _int,
-        [_int, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
-         ctypes.POINTER(_i64)],
-    ),
-    'dqz_c51_optimizer_create': (
-        _int, [ctypes.POINTER(DqzOptimizerConfig), _int, ctypes.POINTER(_vp)]),
-    'dqz_c51_create': (
-        _int, [ctypes.POINTER(DqzLearnerConfig), _int, _vp,
-               ctypes.POINTER(_vp)]),
-    'dqz_c51_destroy': (_int, [_vp]),
-    'dqz_c51_learner': (_int, [_vp, ctypes.POINTER(_vp)]),
-    'dqz_c51_step': (
-        _int,
-        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
-         _vp, _vp]),
-    'dqz_c51_grad': (
-        _int,
-        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
-         _vp]),
-    'dqz_c51_outputs': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'dqz_c51_debug': (_int, [_vp, _vp, _vp, _vp]),
-    'dqz_c51_profile': (
-        _int,
-        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
-         _int, ctypes.POINTER(ctypes.c_float), _vp]),
-    'dqz_c51_forward': (_int, [_vp, _vp, _vp, _int, _vp, _vp]),
-    'dqz_c51_forward_slots': (
-        _int, [_vp, _vp, ctypes.POINTER(DqzStore), _vp, _int, _int, _vp, _vp]),
-    'dqz_c51_act': (
-        _int, [_vp, _vp, _vp, _int, ctypes.c_double, ctypes.c_uint64,
-               ctypes.c_uint64, _vp, _vp]),
-    'dqz_c51_debug_check': (_int, [_int, ctypes.c_uint]),
-    'dqz_qr_param_layout': (
-        _int,
-        [_int, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
-         ctypes.POINTER(_i64)],
-    ),
-    'dqz_qr_optimizer_create': (
-        _int, [ctypes.POINTER(DqzOptimizerConfig), _int, ctypes.POINTER(_vp)]),
-    'dqz_qr_create': (
-        _int, [ctypes.POINTER(DqzLearnerConfig), _int, _vp, ctypes.c_float,
-               ctypes.POINTER(_vp)]),
-    'dqz_qr_destroy': (_int, [_vp]),
-    'dqz_qr_learner': (_int, [_vp, ctypes.POINTER(_vp)]),
-    'dqz_qr_step': (
-        _int,
-        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
-         _vp, _vp]),
-    'dqz_qr_grad': (
-        _int,
-        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
-         _vp]),
-    'dqz_qr_outputs': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'dqz_qr_debug': (_int, [_vp, _vp, _vp, _vp]),
-    'dqz_qr_profile': (
-        _int,
-        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
-         _int, ctypes.POINTER(ctypes.c_float), _vp]),
-    'dqz_qr_forward': (_int, [_vp, _vp, _vp, _int, _vp, _vp]),
-    'dqz_qr_forward_slots': (
-        _int, [_vp, _vp, ctypes.POINTER(DqzStore), _vp, _int, _int, _vp, _vp]),
-    'dqz_qr_act': (
-        _int, [_vp, _vp, _vp, _int, ctypes.c_double, ctypes.c_uint64,
-               ctypes.c_uint64, _vp, _vp]),
-    'dqz_qr_debug_check': (_int, [_int, ctypes.c_uint]),
     'dqz_learner_grad': (
         _int,
         [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
@@ -392,6 +326,47 @@ SIGNATURES = {
     'dqz_meta_debug_stages': (_int, [_vp, _vp, _vp]),
 }
 
+# The wide heads' entries, dqz_c51_<entry> and dqz_qr_<entry>: one signature
+# each but for `create` (the quantile head's also takes huber_param).
+_WIDE_SIGNATURES = {
+    'param_layout': (
+        _int,
+        [_int, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+         ctypes.POINTER(_i64)]),
+    'optimizer_create': (
+        _int, [ctypes.POINTER(DqzOptimizerConfig), _int, ctypes.POINTER(_vp)]),
+    'destroy': (_int, [_vp]),
+    'learner': (_int, [_vp, ctypes.POINTER(_vp)]),
+    'step': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
+         _vp, _vp]),
+    'grad': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
+         _vp]),
+    'outputs': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'debug': (_int, [_vp, _vp, _vp, _vp]),
+    'profile': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
+         _int, ctypes.POINTER(ctypes.c_float), _vp]),
+    'forward': (_int, [_vp, _vp, _vp, _int, _vp, _vp]),
+    'forward_slots': (
+        _int, [_vp, _vp, ctypes.POINTER(DqzStore), _vp, _int, _int, _vp, _vp]),
+    'act': (
+        _int, [_vp, _vp, _vp, _int, ctypes.c_double, ctypes.c_uint64,
+               ctypes.c_uint64, _vp, _vp]),
+    'debug_check': (_int, [_int, ctypes.c_uint]),
+}
+for _prefix in ('dqz_c51_', 'dqz_qr_'):
+  SIGNATURES.update({_prefix + k: v for k, v in _WIDE_SIGNATURES.items()})
+SIGNATURES['dqz_c51_create'] = (
+    _int, [ctypes.POINTER(DqzLearnerConfig), _int, _vp, ctypes.POINTER(_vp)])
+SIGNATURES['dqz_qr_create'] = (
+    _int, [ctypes.POINTER(DqzLearnerConfig), _int, _vp, ctypes.c_float,
+           ctypes.POINTER(_vp)])
+
 _lib = None
 _lock = threading.Lock()
 
@@ -463,35 +438,29 @@ def check(rc):
   return rc
 
 
-def param_layout(num_actions, shared_bias):
-  """Returns (offsets, sizes, total) of the flat parameter buffer."""
+def _layout(entry, num_actions, second):
+  """(offsets, sizes, total) from one of the three *_param_layout entries."""
   offs = (_i64 * NUM_LEAVES)()
   sizes = (_i64 * NUM_LEAVES)()
   total = _i64()
-  check(lib().dqz_param_layout(
-      int(num_actions), int(bool(shared_bias)), offs, sizes,
-      ctypes.byref(total)))
+  check(getattr(lib(), entry)(
+      int(num_actions), int(second), offs, sizes, ctypes.byref(total)))
   return list(offs), list(sizes), int(total.value)
+
+
+def param_layout(num_actions, shared_bias):
+  """Returns (offsets, sizes, total) of the flat parameter buffer."""
+  return _layout('dqz_param_layout', num_actions, bool(shared_bias))
 
 
 def c51_param_layout(num_actions, num_atoms):
   """(offsets, sizes, total) of the categorical network's flat buffer."""
-  offs = (_i64 * NUM_LEAVES)()
-  sizes = (_i64 * NUM_LEAVES)()
-  total = _i64()
-  check(lib().dqz_c51_param_layout(
-      int(num_actions), int(num_atoms), offs, sizes, ctypes.byref(total)))
-  return list(offs), list(sizes), int(total.value)
+  return _layout('dqz_c51_param_layout', num_actions, num_atoms)
 
 
 def qr_param_layout(num_actions, num_quantiles):
   """(offsets, sizes, total) of the quantile network's flat buffer."""
-  offs = (_i64 * NUM_LEAVES)()
-  sizes = (_i64 * NUM_LEAVES)()
-  total = _i64()
-  check(lib().dqz_qr_param_layout(
-      int(num_actions), int(num_quantiles), offs, sizes, ctypes.byref(total)))
-  return list(offs), list(sizes), int(total.value)
+  return _layout('dqz_qr_param_layout', num_actions, num_quantiles)
 
 
 # dqz_c51_debug_check's and dqz_qr_debug_check's request bits (DQZ_C51_REQ_*)

@@ -658,12 +658,12 @@ struct dqz_optimizer {
   float* grad;        // [total] the steps' gradient; padding zero since creation
   double* part;       // [nparts] sums of squares of the last gradient normed
   const float* last;  // the most recent apply's gradient (dqz_optimizer_outputs without clipping)
-  int num_atoms;      // 0: dqz_param_layout; N: the categorical head's layout (dqz_c51_param_layout)
+  int wide_n;         // 0: dqz_param_layout; N: a wide head's layout (dqz_c51_param_layout, dqz_qr_param_layout)
   void* block;
 };
 
-// num_atoms = 0: the scalar head's layout; N: the categorical head's (fc2 leaves A * N wide, no shared bias)
-static int optimizer_create(const dqz_optimizer_config* cfg, int num_atoms, dqz_optimizer** out) {
+// wide_n = 0: the scalar head's layout; N: a wide head's (fc2 leaves A * N wide, no shared bias)
+static int optimizer_create(const dqz_optimizer_config* cfg, int wide_n, dqz_optimizer** out) {
   if (!cfg || !out) return fail(DQZ_ERR_INVALID, "null argument");
   if (cfg->kind != DQZ_OPT_ADAM && cfg->kind != DQZ_OPT_RMSPROP)
     return fail(DQZ_ERR_INVALID, "optimizer kind must be DQZ_OPT_ADAM or DQZ_OPT_RMSPROP");
@@ -675,10 +675,10 @@ static int optimizer_create(const dqz_optimizer_config* cfg, int num_atoms, dqz_
     return fail(DQZ_ERR_INVALID, "decay must be in [0, 1]");
   dqz_optimizer* o = new dqz_optimizer();
   o->cfg = *cfg;
-  o->num_atoms = num_atoms;
+  o->wide_n = wide_n;
   int64_t off[10], sz[10];
-  if (num_atoms)
-    c51_param_layout(cfg->num_actions, num_atoms, off, sz, &o->total);
+  if (wide_n)
+    wide_param_layout(cfg->num_actions, wide_n, off, sz, &o->total);
   else
     param_layout(cfg->num_actions, cfg->shared_bias, off, sz, &o->total);
   for (int i = 0; i < 10; ++i) {
@@ -772,10 +772,10 @@ int dqz_optimizer_outputs(dqz_optimizer* o, float* gnorm, void* stream) {
 
 // What a step in gradient mode followed by dqz_optimizer_apply needs checked before anything is enqueued; the
 // entry has refused a null handle of its own, and L is not read before the layout is compared.
-// num_atoms: 0 for the scalar head, N for the categorical one, whose optimizers have no shared bias
-// (dqz_c51_optimizer_create), as its learner has none.
+// wide: null for the scalar head, else the request's wide head (its N is read behind a live L only), whose
+// optimizers have no shared bias (dqz_c51_optimizer_create, dqz_qr_optimizer_create), as its learner has none.
 static int check_step_apply(const dqz_learner* L, const dqz_params* P, const dqz_optimizer* o, const int32_t* count,
-                            int num_atoms) {
+                            const WideHead* wide) {
   if (!P || !o) return fail(DQZ_ERR_INVALID, "null argument");
   if (!P->online || !P->nu) return fail(DQZ_ERR_INVALID, "null optimizer state");
   if (o->cfg.kind == DQZ_OPT_ADAM && (!P->mu || !count)) return fail(DQZ_ERR_INVALID, "Adam needs mu and count");
@@ -783,7 +783,7 @@ static int check_step_apply(const dqz_learner* L, const dqz_params* P, const dqz
        reinterpret_cast<uintptr_t>(P->mu)) % 16)
     return fail(DQZ_ERR_INVALID, "parameters and moments must be 16-byte aligned");
   if (!L || o->cfg.num_actions != L->cfg.num_actions || (o->cfg.shared_bias != 0) != (L->shared_bias != 0) ||
-      o->num_atoms != num_atoms)
+      o->wide_n != (wide ? wide->N : 0))
     return fail(DQZ_ERR_INVALID, "the optimizer was created for another parameter layout");
   return DQZ_OK;
 }
@@ -791,8 +791,8 @@ static int check_step_apply(const dqz_learner* L, const dqz_params* P, const dqz
 // The request's step in gradient mode into the optimizer's own buffer, then the optimizer on it.  An entry whose
 // request has a draw to build calls check_step_apply ahead of that, so a call is refused for its optimizer first.
 static int step_then_apply(dqz_learner* L, const dqz_params* P, const dqz_store* S, StepRequest r, dqz_optimizer* o,
-                           int32_t* count, int num_atoms, void* stream) {
-  if (int rc = check_step_apply(L, P, o, count, num_atoms)) return rc;
+                           int32_t* count, void* stream) {
+  if (int rc = check_step_apply(L, P, o, count, r.wide)) return rc;
   r.gout = o->grad;
   if (int rc = step_impl(L, P, S, r, stream)) return rc;
   return dqz_optimizer_apply(o, P->online, o->grad, P->mu, P->nu, count, stream);
@@ -801,27 +801,27 @@ static int step_then_apply(dqz_learner* L, const dqz_params* P, const dqz_store*
 int dqz_learner_step_opt(dqz_learner* L, const dqz_params* P, const dqz_store* S, const int32_t* slots,
                          const float* is_weights, dqz_optimizer* o, int32_t* count, void* stream) {
   if (!L) return fail(DQZ_ERR_INVALID, "null argument");
-  return step_then_apply(L, P, S, {.slots = slots, .is_weights = is_weights}, o, count, 0, stream);
+  return step_then_apply(L, P, S, {.slots = slots, .is_weights = is_weights}, o, count, stream);
 }
 
 int dqz_learner_step_opt_uniform(dqz_learner* L, const dqz_params* P, const dqz_store* S, int64_t base, int64_t size,
                                  int64_t capacity, uint64_t seed, uint64_t* counter_dev, int32_t* slots_out,
                                  dqz_optimizer* o, int32_t* count, void* stream) {
   if (!L) return fail(DQZ_ERR_INVALID, "null argument");
-  if (int rc = check_step_apply(L, P, o, count, 0)) return rc;
+  if (int rc = check_step_apply(L, P, o, count, nullptr)) return rc;
   UniformDraw d;
   if (int rc = uniform_draw_args(L, base, size, capacity, seed, counter_dev, slots_out, &d)) return rc;
-  return step_then_apply(L, P, S, {.draw = &d}, o, count, 0, stream);
+  return step_then_apply(L, P, S, {.draw = &d}, o, count, stream);
 }
 
 int dqz_learner_step_opt_per_draw(dqz_learner* L, const dqz_params* P, const dqz_store* S, const dqz_per_draw* d,
                                   dqz_optimizer* o, int32_t* count, void* stream) {
   if (!L) return fail(DQZ_ERR_INVALID, "null argument");
-  if (int rc = check_step_apply(L, P, o, count, 0)) return rc;
+  if (int rc = check_step_apply(L, P, o, count, nullptr)) return rc;
   PerSampleArgs a;
   PerWbArgs wb;
   if (int rc = per_draw_request(L, d, &a, &wb)) return rc;
-  return step_then_apply(L, P, S, {.pd = &a, .wb = &wb}, o, count, 0, stream);
+  return step_then_apply(L, P, S, {.pd = &a, .wb = &wb}, o, count, stream);
 }
 
 int dqz_per_add(double* tree, int64_t cap, int32_t remove_index, int32_t add_index, double priority,
@@ -870,23 +870,27 @@ int dqz_learner_debug_activations(dqz_learner* L, int z, float* y1, float* y2, f
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
-// the categorical (C51) agent (c51.hpp)
+// the categorical (C51) and quantile (QR-DQN) agents (c51.hpp, qr.hpp): one host path, two sets of entries
 
 static_assert(C51_MAX_ATOMS == C51_MAXN && C51_MAX_OUT == C51_MAXOUT, "learner_impl.hpp restates c51.hpp's limits");
+static_assert(QR_MAX_QUANTILES == QR_MAXN && QR_MAX_OUT == QR_MAXOUT, "learner_impl.hpp restates qr.hpp's limits");
 
-// A dqz_learner on the categorical layout plus the head's own buffers.
-struct dqz_c51 {
+// A dqz_learner on the wide layout plus the head's own buffers: what a dqz_c51 and a dqz_qr handle point to.
+struct dqz_wide {
   dqz_learner* L;
   int A, N;
-  C51Head head;  // support and outputs, carved from block
+  WideHead head;  // grid and outputs, carved from block
   void* block;
 };
-static dqz_learner* learner_of(dqz_c51* C) { return C ? C->L : nullptr; }  // null: the shared checks refuse it
+static dqz_wide* wide_of(dqz_c51* C) { return reinterpret_cast<dqz_wide*>(C); }
+static dqz_wide* wide_of(dqz_qr* Q) { return reinterpret_cast<dqz_wide*>(Q); }
+static dqz_learner* learner_of(dqz_wide* W) { return W ? W->L : nullptr; }  // null: the shared checks refuse it
 
-static int c51_check_shape(int A, int N) {
+static int wide_check_shape(WideKind kind, int A, int N) {
+  const WideDesc& d = kWide[kind];
   if (A < 1 || A > MAXA) return fail(DQZ_ERR_INVALID, "num_actions must be in [1, %d]", MAXA);
-  if (N < 2 || N > C51_MAXN) return fail(DQZ_ERR_INVALID, "num_atoms must be in [2, %d]", C51_MAXN);
-  if (A * N > C51_MAXOUT) return fail(DQZ_ERR_INVALID, "num_actions * num_atoms must be <= %d", C51_MAXOUT);
+  if (N < d.min_n || N > d.max_n) return fail(DQZ_ERR_INVALID, "%s must be in [%d, %d]", d.count, d.min_n, d.max_n);
+  if (A * N > d.max_out) return fail(DQZ_ERR_INVALID, "num_actions * %s must be <= %d", d.count, d.max_out);
   return DQZ_OK;
 }
 
@@ -912,225 +916,287 @@ static int c51_logits(dqz_learner* L, const NetZ& nz, int Z, int B, int AN, floa
   return DQZ_OK;
 }
 
-int dqz::c51_launch(C51Launch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, void* stream) {
+// The head kernels' arguments that learn and forward mode share
+static C51HeadArgs c51_head_args(const WideHead& c, int Z, int B, int A) {
+  C51HeadArgs h{};
+  h.logits = c.out;
+  h.support = c.grid;
+  h.Z = Z;
+  h.B = B;
+  h.A = A;
+  h.N = c.N;
+  return h;
+}
+static QrHeadArgs qr_head_args(const WideHead& c, int Z, int B, int A) {
+  QrHeadArgs h{};
+  h.out = c.out;
+  h.tau = c.grid;
+  h.kappa = c.kappa;
+  h.Z = Z;
+  h.B = B;
+  h.A = A;
+  h.N = c.N;
+  return h;
+}
+
+int dqz::wide_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const C51Head& c = *r.c51;
+  const WideHead& c = *r.wide;
+  const bool qr = c.kind == WIDE_QR;
   const int B = L->cfg.batch, A = L->cfg.num_actions, N = c.N;
-  if (which == C51_LOGITS) {
+  if (which == WIDE_OUTPUTS) {
     const NetZ nz{{P->online, P->target, P->online}, {0, 1, 1}};
-    return c51_logits(L, nz, 2, B, A * N, c.logits, st);
+    return c51_logits(L, nz, 2, B, A * N, c.out, st);
   }
-  if (which == C51_HEAD) {
-    C51HeadArgs h{};
-    h.logits = c.logits;
-    h.h1 = L->h1;
-    h.w2 = P->online + L->off[8];
-    h.support = c.support;
-    h.Z = 2;
-    h.B = B;
-    h.A = A;
-    h.N = N;
+  if (which == WIDE_HEAD && qr) {
+    QrHeadArgs h = qr_head_args(c, 2, B, A);
     h.rec = reinterpret_cast<const float4*>(L->rec);
     h.qv = c.qv;
-    h.la = c.la;
-    h.dl = c.dl;
+    h.theta = c.taken;
+    h.dtheta = c.dtaken;
+    h.dout = c.dout;
+    h.astar = c.astar;
+    h.loss_part = L->loss_part;
+    h.gq = L->gq;
+    h.ga = L->ga;
+    hipLaunchKernelGGL(qr_head_kernel, dim3(B), dim3(QR_THREADS), 0, st, h);
+  } else if (which == WIDE_HEAD) {
+    C51HeadArgs h = c51_head_args(c, 2, B, A);
+    h.h1 = L->h1;
+    h.w2 = P->online + L->off[8];
+    h.rec = reinterpret_cast<const float4*>(L->rec);
+    h.qv = c.qv;
+    h.la = c.taken;
+    h.dl = c.dtaken;
     h.astar = c.astar;
     h.loss_part = L->loss_part;
     h.gq = L->gq;
     h.ga = L->ga;
     h.dz1 = L->dz1;
     hipLaunchKernelGGL(c51_head_kernel, dim3(B), dim3(HID), 0, st, h);
-    DQZ_HIP(hipGetLastError());
-    return DQZ_OK;
+  } else if (which == WIDE_DZ1) {  // the quantile head alone (WideHead::dout)
+    QrDz1Args d{};
+    d.dout = c.dout;
+    d.w2 = P->online + L->off[8];
+    d.h1 = L->h1;
+    d.B = B;
+    d.AN = A * N;
+    d.dz1 = L->dz1;
+    hipLaunchKernelGGL(qr_dz1_kernel, dim3(HID / QR_DZ_ROWS, (B + 15) / 16), dim3(64 * QR_DZ_WAVES), 0, st, d);
+  } else if (qr) {  // WIDE_FC2_GRAD
+    QrGradArgs g{};
+    g.h1 = L->h1;
+    g.dout = c.dout;
+    g.B = B;
+    g.AN = A * N;
+    g.gw = r.gout + L->off[8];
+    g.gb = r.gout + L->off[9];
+    g.acc = r.gacc;
+    const dim3 grid(HID / 16 + 1, (A * N + 64 * QR_FG_TILES - 1) / (64 * QR_FG_TILES));
+    hipLaunchKernelGGL(qr_fc2_grad_kernel, grid, dim3(256), 0, st, g);
+  } else {
+    C51GradArgs g{};
+    g.h1 = L->h1;
+    g.dl = c.dtaken;
+    g.ga = L->ga;
+    g.B = B;
+    g.A = A;
+    g.N = N;
+    g.gw = r.gout + L->off[8];
+    g.gb = r.gout + L->off[9];
+    g.acc = r.gacc;
+    const int64_t elems = (int64_t)(HID + 1) * A * N;
+    hipLaunchKernelGGL(c51_fc2_grad_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, g);
   }
-  C51GradArgs g{};
-  g.h1 = L->h1;
-  g.dl = c.dl;
-  g.ga = L->ga;
-  g.B = B;
-  g.A = A;
-  g.N = N;
-  g.gw = r.gout + L->off[8];
-  g.gb = r.gout + L->off[9];
-  g.acc = r.gacc;
-  const int64_t elems = (int64_t)(HID + 1) * A * N;
-  hipLaunchKernelGGL(c51_fc2_grad_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, g);
   DQZ_HIP(hipGetLastError());
   return DQZ_OK;
 }
 
-// q_values of n states through one copy: the torso, the logits, the head in forward mode (actor: with a draw)
-static int c51_forward_q(dqz_c51* C, const float* params, const Conv1Src& src, int which, int n, float* q_out,
-                         const ActorDraw* act, hipStream_t st) {
-  dqz_learner* L = C->L;
+// The head in forward mode: q_values to q_out and, for the actor, its draw
+template <class Args>
+static void set_forward(Args* h, float* q_out, const ActorDraw* act) {
+  h->fwd_only = 1;
+  h->qv = q_out;
+  if (act) {
+    h->act_out = act->out;
+    h->eps = act->eps;
+    h->act_seed = act->seed;
+    h->act_ctr = act->counter;
+  }
+}
+
+// q_values of n states through one copy: the torso, the outputs, the head in forward mode (actor: with a draw)
+static int wide_forward_q(dqz_wide* W, const float* params, const Conv1Src& src, int which, int n, float* q_out,
+                          const ActorDraw* act, hipStream_t st) {
+  dqz_learner* L = W->L;
   if (int rc = forward_torso(L, params, src, which, n, st)) return rc;
   const NetZ nz{{params, params, params}, {which, which, which}};
-  if (int rc = c51_logits(L, nz, 1, n, C->A * C->N, C->head.logits, st)) return rc;
-  C51HeadArgs h{};
-  h.logits = C->head.logits;
-  h.support = C->head.support;
-  h.Z = 1;
-  h.B = n;
-  h.A = C->A;
-  h.N = C->N;
-  h.fwd_only = 1;
-  h.qv = q_out;
-  if (act) {
-    h.act_out = act->out;
-    h.eps = act->eps;
-    h.act_seed = act->seed;
-    h.act_ctr = act->counter;
+  if (int rc = c51_logits(L, nz, 1, n, W->A * W->N, W->head.out, st)) return rc;
+  if (W->head.kind == WIDE_QR) {
+    QrHeadArgs h = qr_head_args(W->head, 1, n, W->A);
+    set_forward(&h, q_out, act);
+    hipLaunchKernelGGL(qr_head_kernel, dim3(n), dim3(QR_THREADS), 0, st, h);
+  } else {
+    C51HeadArgs h = c51_head_args(W->head, 1, n, W->A);
+    set_forward(&h, q_out, act);
+    hipLaunchKernelGGL(c51_head_kernel, dim3(n), dim3(HID), 0, st, h);
   }
-  hipLaunchKernelGGL(c51_head_kernel, dim3(n), dim3(HID), 0, st, h);
   DQZ_HIP(hipGetLastError());
   return DQZ_OK;
 }
 
-extern "C" {
+// The entries' bodies.  A null handle is refused first; of a live one nothing but L is read before the shared
+// checks (forward_src, check_step_apply, check_step) have met a null L.
 
-int dqz_c51_param_layout(int num_actions, int num_atoms, int64_t offsets[10], int64_t sizes[10], int64_t* total) {
-  if (int rc = c51_check_shape(num_actions, num_atoms)) return rc;
+static int wide_layout(WideKind kind, int A, int N, int64_t offsets[10], int64_t sizes[10], int64_t* total) {
+  if (int rc = wide_check_shape(kind, A, N)) return rc;
   if (!offsets || !sizes || !total) return fail(DQZ_ERR_INVALID, "null output pointer");
-  c51_param_layout(num_actions, num_atoms, offsets, sizes, total);
+  wide_param_layout(A, N, offsets, sizes, total);
   return DQZ_OK;
 }
 
-int dqz_c51_optimizer_create(const dqz_optimizer_config* cfg, int num_atoms, dqz_optimizer** out) {
+static int wide_optimizer_create(WideKind kind, const dqz_optimizer_config* cfg, int N, dqz_optimizer** out) {
   if (!cfg || !out) return fail(DQZ_ERR_INVALID, "null argument");
-  if (int rc = c51_check_shape(cfg->num_actions, num_atoms)) return rc;
-  if (cfg->shared_bias) return fail(DQZ_ERR_INVALID, "the categorical head has no shared bias");
-  return optimizer_create(cfg, num_atoms, out);
+  if (int rc = wide_check_shape(kind, cfg->num_actions, N)) return rc;
+  if (cfg->shared_bias) return fail(DQZ_ERR_INVALID, "the %s head has no shared bias", kWide[kind].noun);
+  return optimizer_create(cfg, N, out);  // the wide layout depends on A * N alone
 }
 
-int dqz_c51_create(const dqz_learner_config* cfg, int num_atoms, const float* support, dqz_c51** out) {
-  if (!cfg || !support || !out) return fail(DQZ_ERR_INVALID, "null argument");
-  if (int rc = c51_check_shape(cfg->num_actions, num_atoms)) return rc;
+// What a create refuses of its configuration before it reads the grid: cfg is non-null
+static int wide_check_config(WideKind kind, const dqz_learner_config* cfg, int N) {
+  if (int rc = wide_check_shape(kind, cfg->num_actions, N)) return rc;
   if (cfg->batch < 2 || cfg->batch > MAXB) return fail(DQZ_ERR_INVALID, "batch must be in [2, %d]", MAXB);
-  if (cfg->algo != DQZ_ALGO_DQN) return fail(DQZ_ERR_INVALID, "the categorical head runs on a DQN learner");
-  // the support, checked on the host (this call may synchronise; the step never does)
-  float z[C51_MAXN];
-  DQZ_HIP(hipMemcpy(z, support, sizeof(float) * num_atoms, hipMemcpyDefault));
-  for (int i = 0; i < num_atoms; ++i)
-    if (!std::isfinite(z[i]) || (i > 0 && !(z[i] > z[i - 1])))
-      return fail(DQZ_ERR_INVALID, "support must be finite and strictly increasing (atom %d)", i);
+  if (cfg->algo != DQZ_ALGO_DQN) return fail(DQZ_ERR_INVALID, "the %s head runs on a DQN learner", kWide[kind].noun);
+  return DQZ_OK;
+}
+
+static int wide_destroy(dqz_wide* W) {
+  if (!W) return DQZ_OK;
+  if (W->block) (void)hipFree(W->block);
+  (void)dqz_learner_destroy(W->L);
+  delete W;
+  return DQZ_OK;
+}
+
+// The back half of both creates, behind wide_check_config and the entry's own checks of its grid (host, [N])
+static int wide_create(WideKind kind, const dqz_learner_config* cfg, int N, const float* grid_host, float kappa,
+                       dqz_wide** out) {
+  const WideDesc& d = kWide[kind];
   dqz_learner* L = nullptr;
   if (int rc = dqz_learner_create(cfg, &L)) return rc;
-  const int A = cfg->num_actions, N = num_atoms;
-  c51_param_layout(A, N, L->off, L->sz, &L->total);  // leaves 0-7 unchanged; the scalar head's L->q stays unused
-  dqz_c51* C = new dqz_c51();
-  C->L = L;
-  C->A = A;
-  C->N = N;
-  const int64_t B = cfg->batch;
-  const int64_t n_sup = (N + 63) / 64 * 64, n_lg = 2 * B * A * N, n_la = B * N, n_qv = (2 * B * A + 63) / 64 * 64;
-  const int64_t floats = n_sup + n_lg + 2 * n_la + n_qv + B;
-  if (hipMalloc(&C->block, floats * sizeof(float)) != hipSuccess ||
-      hipMemset(C->block, 0, floats * sizeof(float)) != hipSuccess) {
-    if (C->block) (void)hipFree(C->block);
+  const int A = cfg->num_actions;
+  wide_param_layout(A, N, L->off, L->sz, &L->total);  // leaves 0-7 unchanged; the scalar head's L->q stays unused
+  dqz_wide* W = new dqz_wide();
+  W->L = L;
+  W->A = A;
+  W->N = N;
+  // every piece on a 64-float boundary, in WideHead's order; astar [B] last
+  const auto pad = [](int64_t n) { return (n + 63) / 64 * 64; };
+  const int64_t B = cfg->batch, AN = (int64_t)A * N;
+  const int64_t n_grid = pad(N), n_out = pad(2 * B * AN), n_tk = pad(B * N);
+  const int64_t n_do = kind == WIDE_QR ? pad(B * AN + QR_PAD) : 0, n_qv = pad(2 * B * A);
+  const int64_t floats = n_grid + n_out + 2 * n_tk + n_do + n_qv + B;
+  if (hipMalloc(&W->block, floats * sizeof(float)) != hipSuccess ||
+      hipMemset(W->block, 0, floats * sizeof(float)) != hipSuccess) {
+    if (W->block) (void)hipFree(W->block);
     (void)dqz_learner_destroy(L);
-    delete C;
-    return fail(DQZ_ERR_HIP, "hipMalloc of %lld bytes of categorical-head scratch failed", (long long)(floats * 4));
+    delete W;
+    return fail(DQZ_ERR_HIP, "hipMalloc of %lld bytes of %s-head scratch failed", (long long)(floats * 4), d.noun);
   }
-  float* p = (float*)C->block;
-  float* sup = p;
-  C->head.N = N;
-  C->head.support = sup;
-  C->head.logits = p + n_sup;
-  C->head.la = C->head.logits + n_lg;
-  C->head.dl = C->head.la + n_la;
-  C->head.qv = C->head.dl + n_la;
-  C->head.astar = reinterpret_cast<int32_t*>(C->head.qv + n_qv);
-  if (hipMemcpy(sup, z, sizeof(float) * N, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)dqz_c51_destroy(C);
-    return fail(DQZ_ERR_HIP, "copy of the support failed");
+  float* p = (float*)W->block;
+  WideHead& h = W->head;
+  h.kind = kind;
+  h.N = N;
+  h.grid = p;
+  h.kappa = kappa;
+  h.out = p + n_grid;
+  h.taken = h.out + n_out;
+  h.dtaken = h.taken + n_tk;
+  h.dout = n_do ? h.dtaken + n_tk : nullptr;
+  h.qv = h.dtaken + n_tk + n_do;
+  h.astar = reinterpret_cast<int32_t*>(h.qv + n_qv);
+  if (hipMemcpy(p, grid_host, sizeof(float) * N, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)wide_destroy(W);
+    return fail(DQZ_ERR_HIP, "copy of the %s failed", d.grid);
   }
-  *out = C;
+  *out = W;
   return DQZ_OK;
 }
 
-int dqz_c51_destroy(dqz_c51* C) {
-  if (!C) return DQZ_OK;
-  if (C->block) (void)hipFree(C->block);
-  (void)dqz_learner_destroy(C->L);
-  delete C;
+static int wide_learner(dqz_wide* W, dqz_learner** out) {
+  if (!W || !out) return fail(DQZ_ERR_INVALID, "null argument");
+  *out = W->L;
   return DQZ_OK;
 }
 
-int dqz_c51_learner(dqz_c51* C, dqz_learner** out) {
-  if (!C || !out) return fail(DQZ_ERR_INVALID, "null argument");
-  *out = C->L;
-  return DQZ_OK;
+static int wide_step(dqz_wide* W, const dqz_params* P, const dqz_store* S, const int32_t* slots, dqz_optimizer* o,
+                     int32_t* count, void* stream) {
+  if (!W) return fail(DQZ_ERR_INVALID, "null argument");
+  return step_then_apply(W->L, P, S, {.slots = slots, .wide = &W->head}, o, count, stream);
 }
 
-int dqz_c51_step(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, dqz_optimizer* o,
-                 int32_t* count, void* stream) {
-  if (!C) return fail(DQZ_ERR_INVALID, "null argument");
-  return step_then_apply(C->L, P, S, {.slots = slots, .c51 = &C->head}, o, count, C->N, stream);
-}
-
-int dqz_c51_grad(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
-                 void* stream) {
-  if (!C) return fail(DQZ_ERR_INVALID, "null argument");
+static int wide_grad(dqz_wide* W, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
+                     void* stream) {
+  if (!W) return fail(DQZ_ERR_INVALID, "null argument");
   if (!grad_out) return fail(DQZ_ERR_INVALID, "null grad_out");
-  return step_impl(C->L, P, S, {.slots = slots, .gout = grad_out, .c51 = &C->head}, stream);
+  return step_impl(W->L, P, S, {.slots = slots, .gout = grad_out, .wide = &W->head}, stream);
 }
 
-int dqz_c51_profile(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
-                    int iters, float* phase_ms, void* stream) {
-  if (!C) return fail(DQZ_ERR_INVALID, "null argument");
+static int wide_profile(dqz_wide* W, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
+                        int iters, float* phase_ms, void* stream) {
+  if (!W) return fail(DQZ_ERR_INVALID, "null argument");
   if (!grad_out) return fail(DQZ_ERR_INVALID, "null grad_out");
-  return profile_step(C->L, P, S, {.slots = slots, .gout = grad_out, .c51 = &C->head}, iters, phase_ms, stream);
+  return profile_step(W->L, P, S, {.slots = slots, .gout = grad_out, .wide = &W->head}, iters, phase_ms, stream);
 }
 
-int dqz_c51_outputs(dqz_c51* C, float* logits_a, float* q_values, float* loss_b, float* loss, int32_t* a_star,
-                    void* stream) {
-  if (!C) return fail(DQZ_ERR_INVALID, "null argument");
+static int wide_outputs(dqz_wide* W, float* taken, float* q_values, float* loss_b, float* loss, int32_t* a_star,
+                        void* stream) {
+  if (!W) return fail(DQZ_ERR_INVALID, "null argument");
   hipStream_t st = (hipStream_t)stream;
-  const int64_t B = C->L->cfg.batch;
+  const int64_t B = W->L->cfg.batch;
   const struct {
     void* dst;
     const void* src;
     int64_t n;
-  } rows[] = {{logits_a, C->head.la, B * C->N},  {q_values, C->head.qv, 2 * B * C->A}, {loss_b, C->L->loss_part, B},
-              {loss, C->L->loss, 1},             {a_star, C->head.astar, B}};
+  } rows[] = {{taken, W->head.taken, B * W->N},  {q_values, W->head.qv, 2 * B * W->A}, {loss_b, W->L->loss_part, B},
+              {loss, W->L->loss, 1},             {a_star, W->head.astar, B}};
   for (const auto& r : rows)
     if (r.dst) DQZ_HIP(hipMemcpyAsync(r.dst, r.src, 4 * r.n, hipMemcpyDeviceToDevice, st));
   return DQZ_OK;
 }
 
-int dqz_c51_debug(dqz_c51* C, float* logits, float* dlogits, void* stream) {
-  if (!C) return fail(DQZ_ERR_INVALID, "null argument");
+static int wide_debug(dqz_wide* W, float* outputs, float* dtaken, void* stream) {
+  if (!W) return fail(DQZ_ERR_INVALID, "null argument");
   hipStream_t st = (hipStream_t)stream;
-  const int64_t B = C->L->cfg.batch;
-  if (logits)
-    DQZ_HIP(hipMemcpyAsync(logits, C->head.logits, 4 * 2 * B * C->A * C->N, hipMemcpyDeviceToDevice, st));
-  if (dlogits) DQZ_HIP(hipMemcpyAsync(dlogits, C->head.dl, 4 * B * C->N, hipMemcpyDeviceToDevice, st));
+  const int64_t B = W->L->cfg.batch;
+  if (outputs) DQZ_HIP(hipMemcpyAsync(outputs, W->head.out, 4 * 2 * B * W->A * W->N, hipMemcpyDeviceToDevice, st));
+  if (dtaken) DQZ_HIP(hipMemcpyAsync(dtaken, W->head.dtaken, 4 * B * W->N, hipMemcpyDeviceToDevice, st));
   return DQZ_OK;
 }
 
-int dqz_c51_forward(dqz_c51* C, const float* params, const uint8_t* states, int n, float* q_out, void* stream) {
+static int wide_forward(dqz_wide* W, const float* params, const uint8_t* states, int n, float* q_out, void* stream) {
   Conv1Src src;
-  if (int rc = forward_src(learner_of(C), params, n, {.states = states, .q_out = q_out}, &src)) return rc;
-  return c51_forward_q(C, params, src, 0, n, q_out, nullptr, (hipStream_t)stream);
+  if (int rc = forward_src(learner_of(W), params, n, {.states = states, .q_out = q_out}, &src)) return rc;
+  return wide_forward_q(W, params, src, 0, n, q_out, nullptr, (hipStream_t)stream);
 }
 
-int dqz_c51_forward_slots(dqz_c51* C, const float* params, const dqz_store* S, const int32_t* slots, int n, int which,
-                          float* q_out, void* stream) {
+static int wide_forward_slots(dqz_wide* W, const float* params, const dqz_store* S, const int32_t* slots, int n,
+                              int which, float* q_out, void* stream) {
   Conv1Src src;
   const ForwardInput in{.from_store = true, .store = S, .slots = slots, .which = which, .q_out = q_out};
-  if (int rc = forward_src(learner_of(C), params, n, in, &src)) return rc;
-  return c51_forward_q(C, params, src, which, n, q_out, nullptr, (hipStream_t)stream);
+  if (int rc = forward_src(learner_of(W), params, n, in, &src)) return rc;
+  return wide_forward_q(W, params, src, which, n, q_out, nullptr, (hipStream_t)stream);
 }
 
-int dqz_c51_act(dqz_c51* C, const float* params, const uint8_t* states, int n, double epsilon, uint64_t seed,
-                uint64_t counter, dqz_action* out, void* stream) {
+static int wide_act(dqz_wide* W, const float* params, const uint8_t* states, int n, double epsilon, uint64_t seed,
+                    uint64_t counter, dqz_action* out, void* stream) {
   ActorDraw act{epsilon, seed, counter, out};
   Conv1Src src;
-  if (int rc = forward_src(learner_of(C), params, n, {.states = states, .act = &act}, &src)) return rc;
-  return c51_forward_q(C, params, src, 0, n, C->head.qv, &act, (hipStream_t)stream);
+  if (int rc = forward_src(learner_of(W), params, n, {.states = states, .act = &act}, &src)) return rc;
+  return wide_forward_q(W, params, src, 0, n, W->head.qv, &act, (hipStream_t)stream);
 }
 
-int dqz_c51_debug_check(int batch, unsigned request) {
+static int wide_debug_check(WideKind kind, int batch, unsigned request) {
   // a host-only learner, parameters and store whose pointers are set but never followed: check_step alone runs
   static float word[4];
   dqz_learner L{};
@@ -1156,11 +1222,12 @@ int dqz_c51_debug_check(int batch, unsigned request) {
   const Rms epi{};
   const MetaSoftmax msm{};
   const PerWbArgs wb{};
-  const C51Head head{};
+  WideHead head{};
+  head.kind = kind;
   StepRequest r{};
   r.slots = iw;
   r.gout = word;
-  r.c51 = &head;
+  r.wide = &head;
   if (request & DQZ_C51_REQ_WEIGHTS) r.is_weights = word;
   if (request & DQZ_C51_REQ_PER_DRAW) r.pd = &pd;
   if (request & DQZ_C51_REQ_UNIFORM_DRAW) r.draw = &draw;
@@ -1175,133 +1242,24 @@ int dqz_c51_debug_check(int batch, unsigned request) {
   return check_step(&L, &P, &S, r);
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// the quantile (QR-DQN) agent (qr.hpp)
-
-static_assert(QR_MAX_QUANTILES == QR_MAXN && QR_MAX_OUT == QR_MAXOUT, "learner_impl.hpp restates qr.hpp's limits");
-
-// A dqz_learner on the quantile layout plus the head's own buffers.
-struct dqz_qr {
-  dqz_learner* L;
-  int A, N;
-  QrHead head;  // quantiles and outputs, carved from block
-  void* block;
-};
-static dqz_learner* learner_of(dqz_qr* Q) { return Q ? Q->L : nullptr; }  // null: the shared checks refuse it
-
-static int qr_check_shape(int A, int N) {
-  if (A < 1 || A > MAXA) return fail(DQZ_ERR_INVALID, "num_actions must be in [1, %d]", MAXA);
-  if (N < 1 || N > QR_MAXN) return fail(DQZ_ERR_INVALID, "num_quantiles must be in [1, %d]", QR_MAXN);
-  if (A * N > QR_MAXOUT) return fail(DQZ_ERR_INVALID, "num_actions * num_quantiles must be <= %d", QR_MAXOUT);
-  return DQZ_OK;
-}
-
-static QrHeadArgs qr_head_args(const QrHead& c, int Z, int B, int A) {
-  QrHeadArgs h{};
-  h.out = c.out;
-  h.tau = c.tau;
-  h.kappa = c.kappa;
-  h.Z = Z;
-  h.B = B;
-  h.A = A;
-  h.N = c.N;
-  return h;
-}
-
-int dqz::qr_launch(QrLaunch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const QrHead& c = *r.qr;
-  const int B = L->cfg.batch, A = L->cfg.num_actions, N = c.N;
-  if (which == QR_OUTPUTS) {
-    const NetZ nz{{P->online, P->target, P->online}, {0, 1, 1}};
-    return c51_logits(L, nz, 2, B, A * N, c.out, st);
-  }
-  if (which == QR_HEAD) {
-    QrHeadArgs h = qr_head_args(c, 2, B, A);
-    h.rec = reinterpret_cast<const float4*>(L->rec);
-    h.qv = c.qv;
-    h.theta = c.theta;
-    h.dtheta = c.dtheta;
-    h.dout = c.dout;
-    h.astar = c.astar;
-    h.loss_part = L->loss_part;
-    h.gq = L->gq;
-    h.ga = L->ga;
-    hipLaunchKernelGGL(qr_head_kernel, dim3(B), dim3(QR_THREADS), 0, st, h);
-    DQZ_HIP(hipGetLastError());
-    return DQZ_OK;
-  }
-  if (which == QR_DZ1) {
-    QrDz1Args d{};
-    d.dout = c.dout;
-    d.w2 = P->online + L->off[8];
-    d.h1 = L->h1;
-    d.B = B;
-    d.AN = A * N;
-    d.dz1 = L->dz1;
-    hipLaunchKernelGGL(qr_dz1_kernel, dim3(HID / QR_DZ_ROWS, (B + 15) / 16), dim3(64 * QR_DZ_WAVES), 0, st, d);
-    DQZ_HIP(hipGetLastError());
-    return DQZ_OK;
-  }
-  QrGradArgs g{};
-  g.h1 = L->h1;
-  g.dout = c.dout;
-  g.B = B;
-  g.AN = A * N;
-  g.gw = r.gout + L->off[8];
-  g.gb = r.gout + L->off[9];
-  g.acc = r.gacc;
-  const dim3 grid(HID / 16 + 1, (A * N + 64 * QR_FG_TILES - 1) / (64 * QR_FG_TILES));
-  hipLaunchKernelGGL(qr_fc2_grad_kernel, grid, dim3(256), 0, st, g);
-  DQZ_HIP(hipGetLastError());
-  return DQZ_OK;
-}
-
-// q_values of n states through one copy: the torso, the outputs, the head in forward mode (actor: with a draw)
-static int qr_forward_q(dqz_qr* Q, const float* params, const Conv1Src& src, int which, int n, float* q_out,
-                        const ActorDraw* act, hipStream_t st) {
-  dqz_learner* L = Q->L;
-  if (int rc = forward_torso(L, params, src, which, n, st)) return rc;
-  const NetZ nz{{params, params, params}, {which, which, which}};
-  if (int rc = c51_logits(L, nz, 1, n, Q->A * Q->N, Q->head.out, st)) return rc;
-  QrHeadArgs h = qr_head_args(Q->head, 1, n, Q->A);
-  h.fwd_only = 1;
-  h.qv = q_out;
-  if (act) {
-    h.act_out = act->out;
-    h.eps = act->eps;
-    h.act_seed = act->seed;
-    h.act_ctr = act->counter;
-  }
-  hipLaunchKernelGGL(qr_head_kernel, dim3(n), dim3(QR_THREADS), 0, st, h);
-  DQZ_HIP(hipGetLastError());
-  return DQZ_OK;
-}
-
 extern "C" {
 
-int dqz_qr_param_layout(int num_actions, int num_quantiles, int64_t offsets[10], int64_t sizes[10], int64_t* total) {
-  if (int rc = qr_check_shape(num_actions, num_quantiles)) return rc;
-  if (!offsets || !sizes || !total) return fail(DQZ_ERR_INVALID, "null output pointer");
-  qr_param_layout(num_actions, num_quantiles, offsets, sizes, total);
-  return DQZ_OK;
-}
-
-int dqz_qr_optimizer_create(const dqz_optimizer_config* cfg, int num_quantiles, dqz_optimizer** out) {
-  if (!cfg || !out) return fail(DQZ_ERR_INVALID, "null argument");
-  if (int rc = qr_check_shape(cfg->num_actions, num_quantiles)) return rc;
-  if (cfg->shared_bias) return fail(DQZ_ERR_INVALID, "the quantile head has no shared bias");
-  return optimizer_create(cfg, num_quantiles, out);  // the wide layout depends on A * N alone
+int dqz_c51_create(const dqz_learner_config* cfg, int num_atoms, const float* support, dqz_c51** out) {
+  if (!cfg || !support || !out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (int rc = wide_check_config(WIDE_C51, cfg, num_atoms)) return rc;
+  // the support, checked on the host (this call may synchronise; the step never does)
+  float z[C51_MAXN];
+  DQZ_HIP(hipMemcpy(z, support, sizeof(float) * num_atoms, hipMemcpyDefault));
+  for (int i = 0; i < num_atoms; ++i)
+    if (!std::isfinite(z[i]) || (i > 0 && !(z[i] > z[i - 1])))
+      return fail(DQZ_ERR_INVALID, "support must be finite and strictly increasing (atom %d)", i);
+  return wide_create(WIDE_C51, cfg, num_atoms, z, 0.f, reinterpret_cast<dqz_wide**>(out));
 }
 
 int dqz_qr_create(const dqz_learner_config* cfg, int num_quantiles, const float* quantiles, float huber_param,
                   dqz_qr** out) {
   if (!cfg || !quantiles || !out) return fail(DQZ_ERR_INVALID, "null argument");
-  if (int rc = qr_check_shape(cfg->num_actions, num_quantiles)) return rc;
-  if (cfg->batch < 2 || cfg->batch > MAXB) return fail(DQZ_ERR_INVALID, "batch must be in [2, %d]", MAXB);
-  if (cfg->algo != DQZ_ALGO_DQN) return fail(DQZ_ERR_INVALID, "the quantile head runs on a DQN learner");
+  if (int rc = wide_check_config(WIDE_QR, cfg, num_quantiles)) return rc;
   if (!std::isfinite(huber_param) || !(huber_param > 0.f))
     return fail(DQZ_ERR_INVALID,
                 "huber_param must be finite and > 0 (huber_param = 0, rlax's plain |delta| branch, is not built); "
@@ -1312,168 +1270,88 @@ int dqz_qr_create(const dqz_learner_config* cfg, int num_quantiles, const float*
   for (int i = 0; i < num_quantiles; ++i)
     if (!std::isfinite(tau[i]) || !(tau[i] > 0.f && tau[i] < 1.f))
       return fail(DQZ_ERR_INVALID, "quantiles must be finite and strictly inside (0, 1) (quantile %d)", i);
-  dqz_learner* L = nullptr;
-  if (int rc = dqz_learner_create(cfg, &L)) return rc;
-  const int A = cfg->num_actions, N = num_quantiles;
-  qr_param_layout(A, N, L->off, L->sz, &L->total);  // leaves 0-7 unchanged; the scalar head's L->q stays unused
-  dqz_qr* Q = new dqz_qr();
-  Q->L = L;
-  Q->A = A;
-  Q->N = N;
-  const int64_t B = cfg->batch;
-  const int64_t n_tau = (N + 63) / 64 * 64, n_out = 2 * B * A * N, n_th = (B * N + 63) / 64 * 64;
-  const int64_t n_do = (B * A * N + QR_PAD + 63) / 64 * 64, n_qv = (2 * B * A + 63) / 64 * 64;
-  const int64_t floats = n_tau + (n_out + 63) / 64 * 64 + 2 * n_th + n_do + n_qv + B;
-  if (hipMalloc(&Q->block, floats * sizeof(float)) != hipSuccess ||
-      hipMemset(Q->block, 0, floats * sizeof(float)) != hipSuccess) {
-    if (Q->block) (void)hipFree(Q->block);
-    (void)dqz_learner_destroy(L);
-    delete Q;
-    return fail(DQZ_ERR_HIP, "hipMalloc of %lld bytes of quantile-head scratch failed", (long long)(floats * 4));
-  }
-  float* p = (float*)Q->block;
-  Q->head.N = N;
-  Q->head.tau = p;
-  Q->head.kappa = huber_param;
-  Q->head.out = p + n_tau;
-  Q->head.theta = Q->head.out + (n_out + 63) / 64 * 64;
-  Q->head.dtheta = Q->head.theta + n_th;
-  Q->head.dout = Q->head.dtheta + n_th;
-  Q->head.qv = Q->head.dout + n_do;
-  Q->head.astar = reinterpret_cast<int32_t*>(Q->head.qv + n_qv);
-  if (hipMemcpy(p, tau, sizeof(float) * N, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)dqz_qr_destroy(Q);
-    return fail(DQZ_ERR_HIP, "copy of the quantiles failed");
-  }
-  *out = Q;
-  return DQZ_OK;
+  return wide_create(WIDE_QR, cfg, num_quantiles, tau, huber_param, reinterpret_cast<dqz_wide**>(out));
 }
 
-int dqz_qr_destroy(dqz_qr* Q) {
-  if (!Q) return DQZ_OK;
-  if (Q->block) (void)hipFree(Q->block);
-  (void)dqz_learner_destroy(Q->L);
-  delete Q;
-  return DQZ_OK;
+int dqz_c51_param_layout(int num_actions, int num_atoms, int64_t offsets[10], int64_t sizes[10], int64_t* total) {
+  return wide_layout(WIDE_C51, num_actions, num_atoms, offsets, sizes, total);
 }
-
-int dqz_qr_learner(dqz_qr* Q, dqz_learner** out) {
-  if (!Q || !out) return fail(DQZ_ERR_INVALID, "null argument");
-  *out = Q->L;
-  return DQZ_OK;
+int dqz_c51_optimizer_create(const dqz_optimizer_config* cfg, int num_atoms, dqz_optimizer** out) {
+  return wide_optimizer_create(WIDE_C51, cfg, num_atoms, out);
 }
+int dqz_c51_destroy(dqz_c51* C) { return wide_destroy(wide_of(C)); }
+int dqz_c51_learner(dqz_c51* C, dqz_learner** out) { return wide_learner(wide_of(C), out); }
+int dqz_c51_step(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, dqz_optimizer* o,
+                 int32_t* count, void* stream) {
+  return wide_step(wide_of(C), P, S, slots, o, count, stream);
+}
+int dqz_c51_grad(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
+                 void* stream) {
+  return wide_grad(wide_of(C), P, S, slots, grad_out, stream);
+}
+int dqz_c51_profile(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
+                    int iters, float* phase_ms, void* stream) {
+  return wide_profile(wide_of(C), P, S, slots, grad_out, iters, phase_ms, stream);
+}
+int dqz_c51_outputs(dqz_c51* C, float* logits_a, float* q_values, float* loss_b, float* loss, int32_t* a_star,
+                    void* stream) {
+  return wide_outputs(wide_of(C), logits_a, q_values, loss_b, loss, a_star, stream);
+}
+int dqz_c51_debug(dqz_c51* C, float* logits, float* dlogits, void* stream) {
+  return wide_debug(wide_of(C), logits, dlogits, stream);
+}
+int dqz_c51_forward(dqz_c51* C, const float* params, const uint8_t* states, int n, float* q_out, void* stream) {
+  return wide_forward(wide_of(C), params, states, n, q_out, stream);
+}
+int dqz_c51_forward_slots(dqz_c51* C, const float* params, const dqz_store* S, const int32_t* slots, int n, int which,
+                          float* q_out, void* stream) {
+  return wide_forward_slots(wide_of(C), params, S, slots, n, which, q_out, stream);
+}
+int dqz_c51_act(dqz_c51* C, const float* params, const uint8_t* states, int n, double epsilon, uint64_t seed,
+                uint64_t counter, dqz_action* out, void* stream) {
+  return wide_act(wide_of(C), params, states, n, epsilon, seed, counter, out, stream);
+}
+int dqz_c51_debug_check(int batch, unsigned request) { return wide_debug_check(WIDE_C51, batch, request); }
 
+int dqz_qr_param_layout(int num_actions, int num_quantiles, int64_t offsets[10], int64_t sizes[10], int64_t* total) {
+  return wide_layout(WIDE_QR, num_actions, num_quantiles, offsets, sizes, total);
+}
+int dqz_qr_optimizer_create(const dqz_optimizer_config* cfg, int num_quantiles, dqz_optimizer** out) {
+  return wide_optimizer_create(WIDE_QR, cfg, num_quantiles, out);
+}
+int dqz_qr_destroy(dqz_qr* Q) { return wide_destroy(wide_of(Q)); }
+int dqz_qr_learner(dqz_qr* Q, dqz_learner** out) { return wide_learner(wide_of(Q), out); }
 int dqz_qr_step(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, dqz_optimizer* o,
                 int32_t* count, void* stream) {
-  if (!Q) return fail(DQZ_ERR_INVALID, "null argument");
-  return step_then_apply(Q->L, P, S, {.slots = slots, .qr = &Q->head}, o, count, Q->N, stream);
+  return wide_step(wide_of(Q), P, S, slots, o, count, stream);
 }
-
 int dqz_qr_grad(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
                 void* stream) {
-  if (!Q) return fail(DQZ_ERR_INVALID, "null argument");
-  if (!grad_out) return fail(DQZ_ERR_INVALID, "null grad_out");
-  return step_impl(Q->L, P, S, {.slots = slots, .gout = grad_out, .qr = &Q->head}, stream);
+  return wide_grad(wide_of(Q), P, S, slots, grad_out, stream);
 }
-
 int dqz_qr_profile(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
                    int iters, float* phase_ms, void* stream) {
-  if (!Q) return fail(DQZ_ERR_INVALID, "null argument");
-  if (!grad_out) return fail(DQZ_ERR_INVALID, "null grad_out");
-  return profile_step(Q->L, P, S, {.slots = slots, .gout = grad_out, .qr = &Q->head}, iters, phase_ms, stream);
+  return wide_profile(wide_of(Q), P, S, slots, grad_out, iters, phase_ms, stream);
 }
-
 int dqz_qr_outputs(dqz_qr* Q, float* theta, float* q_values, float* loss_b, float* loss, int32_t* a_star,
                    void* stream) {
-  if (!Q) return fail(DQZ_ERR_INVALID, "null argument");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t B = Q->L->cfg.batch;
-  const struct {
-    void* dst;
-    const void* src;
-    int64_t n;
-  } rows[] = {{theta, Q->head.theta, B * Q->N},  {q_values, Q->head.qv, 2 * B * Q->A}, {loss_b, Q->L->loss_part, B},
-              {loss, Q->L->loss, 1},             {a_star, Q->head.astar, B}};
-  for (const auto& r : rows)
-    if (r.dst) DQZ_HIP(hipMemcpyAsync(r.dst, r.src, 4 * r.n, hipMemcpyDeviceToDevice, st));
-  return DQZ_OK;
+  return wide_outputs(wide_of(Q), theta, q_values, loss_b, loss, a_star, stream);
 }
-
 int dqz_qr_debug(dqz_qr* Q, float* outputs, float* dtheta, void* stream) {
-  if (!Q) return fail(DQZ_ERR_INVALID, "null argument");
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t B = Q->L->cfg.batch;
-  if (outputs) DQZ_HIP(hipMemcpyAsync(outputs, Q->head.out, 4 * 2 * B * Q->A * Q->N, hipMemcpyDeviceToDevice, st));
-  if (dtheta) DQZ_HIP(hipMemcpyAsync(dtheta, Q->head.dtheta, 4 * B * Q->N, hipMemcpyDeviceToDevice, st));
-  return DQZ_OK;
+  return wide_debug(wide_of(Q), outputs, dtheta, stream);
 }
-
 int dqz_qr_forward(dqz_qr* Q, const float* params, const uint8_t* states, int n, float* q_out, void* stream) {
-  Conv1Src src;
-  if (int rc = forward_src(learner_of(Q), params, n, {.states = states, .q_out = q_out}, &src)) return rc;
-  return qr_forward_q(Q, params, src, 0, n, q_out, nullptr, (hipStream_t)stream);
+  return wide_forward(wide_of(Q), params, states, n, q_out, stream);
 }
-
 int dqz_qr_forward_slots(dqz_qr* Q, const float* params, const dqz_store* S, const int32_t* slots, int n, int which,
                          float* q_out, void* stream) {
-  Conv1Src src;
-  const ForwardInput in{.from_store = true, .store = S, .slots = slots, .which = which, .q_out = q_out};
-  if (int rc = forward_src(learner_of(Q), params, n, in, &src)) return rc;
-  return qr_forward_q(Q, params, src, which, n, q_out, nullptr, (hipStream_t)stream);
+  return wide_forward_slots(wide_of(Q), params, S, slots, n, which, q_out, stream);
 }
-
 int dqz_qr_act(dqz_qr* Q, const float* params, const uint8_t* states, int n, double epsilon, uint64_t seed,
                uint64_t counter, dqz_action* out, void* stream) {
-  ActorDraw act{epsilon, seed, counter, out};
-  Conv1Src src;
-  if (int rc = forward_src(learner_of(Q), params, n, {.states = states, .act = &act}, &src)) return rc;
-  return qr_forward_q(Q, params, src, 0, n, Q->head.qv, &act, (hipStream_t)stream);
+  return wide_act(wide_of(Q), params, states, n, epsilon, seed, counter, out, stream);
 }
-
-int dqz_qr_debug_check(int batch, unsigned request) {
-  // as dqz_c51_debug_check: host structures whose pointers are set but never followed; check_step alone runs
-  static float word[4];
-  dqz_learner L{};
-  L.cfg.batch = batch;
-  L.cfg.num_actions = 6;
-  L.cfg.algo = DQZ_ALGO_DQN;
-  const dqz_params P{word, word, word, word};
-  dqz_store S{};
-  S.frames = reinterpret_cast<uint8_t*>(word);
-  S.fidx = reinterpret_cast<int32_t*>(word);
-  S.action = reinterpret_cast<int32_t*>(word);
-  S.reward = S.discount = word;
-  S.capacity = 1;
-  int32_t* iw = reinterpret_cast<int32_t*>(word);
-  UniformDraw draw{};
-  draw.slots_out = iw;
-  SoftmaxDraw sm{};
-  sm.slots_out = iw;
-  SoftmaxDrawExact smx{};
-  smx.slots_out = iw;
-  PerSampleArgs pd{};
-  pd.out_slots = iw;
-  const Rms epi{};
-  const MetaSoftmax msm{};
-  const PerWbArgs wb{};
-  const QrHead head{};
-  StepRequest r{};
-  r.slots = iw;
-  r.gout = word;
-  r.qr = &head;
-  if (request & DQZ_C51_REQ_WEIGHTS) r.is_weights = word;
-  if (request & DQZ_C51_REQ_PER_DRAW) r.pd = &pd;
-  if (request & DQZ_C51_REQ_UNIFORM_DRAW) r.draw = &draw;
-  if (request & DQZ_C51_REQ_LOGIT_DRAW) r.sm = &sm;
-  if (request & DQZ_C51_REQ_EXACT_DRAW) r.smx = &smx;
-  if (request & DQZ_C51_REQ_META_P) r.meta_p = word;
-  if (request & DQZ_C51_REQ_META_EPI) r.meta_epi = &epi;
-  if (request & DQZ_C51_REQ_META_SOFTMAX) r.meta_sm = &msm;
-  if (request & DQZ_C51_REQ_UNIT) r.unit = 1;
-  if (request & DQZ_C51_REQ_WRITE_BACK) r.wb = &wb;
-  if (request & DQZ_C51_REQ_FUSED_RMSPROP) r.gout = nullptr;
-  return check_step(&L, &P, &S, r);
-}
+int dqz_qr_debug_check(int batch, unsigned request) { return wide_debug_check(WIDE_QR, batch, request); }
 
 }  // extern "C"
 

@@ -229,43 +229,48 @@ struct MetaSoftmax {
   float *x_out, *p_out;
 };
 
-// The categorical (C51) head in place of the scalar one (StepRequest::c51; c51.hpp): the learner's parameter
-// layout then ends in fc2 leaves A * N wide (c51_param_layout), the step runs in gradient mode, and the head's
-// and the fc2 gradient's launches, which live in the other code object, are made by c51_launch.
-struct C51Head {
-  int N;                 // atoms per action
-  const float* support;  // [N] device, strictly increasing
-  float* logits;         // [2][B][A N] online(s_tm1), target(s_t)
-  float* la;             // [B][N] online logits of the taken action
-  float* dl;             // [B][N] d loss / d those logits
-  float* qv;             // [2][B][A] q_values
-  int32_t* astar;        // [B] argmax_a q_values of the target copy
+// A wide head in place of the scalar one (StepRequest::wide): the categorical (C51; c51.hpp) or the quantile
+// (QR-DQN; qr.hpp) one.  The learner's parameter layout then ends in fc2 leaves A * N wide (wide_param_layout;
+// the quantile head's columns are quantile-major, i A + a), the step runs in gradient mode, and the head's and
+// the fc2 gradient's launches, which live in the other code object, are made by wide_launch.
+enum WideKind { WIDE_C51, WIDE_QR };
+struct WideHead {
+  WideKind kind;
+  int N;              // atoms / quantiles per action
+  const float* grid;  // [N] device: the support, strictly increasing / tau, each strictly inside (0, 1)
+  float kappa;        // huber_param > 0 (quantile head only)
+  float* out;         // [2][B][A N] online(s_tm1), target(s_t): logits / quantile outputs
+  float* taken;       // [B][N] online outputs of the taken action (la / theta)
+  float* dtaken;      // [B][N] d loss / d those outputs (dl / dtheta)
+  float* dout;        // [B][A N] (+ QR_PAD) the dense cotangent of the online outputs; null for the categorical
+                      // head, whose head kernel writes dz1 itself
+  float* qv;          // [2][B][A] q_values
+  int32_t* astar;     // [B] argmax_a q_values of the target copy
 };
-constexpr int C51_MAX_ATOMS = 64, C51_MAX_OUT = 1024;  // c51.hpp's C51_MAXN / C51_MAXOUT
-inline void c51_param_layout(int A, int N, int64_t off[10], int64_t sz[10], int64_t* total) {
+constexpr int C51_MAX_ATOMS = 64, C51_MAX_OUT = 1024;     // c51.hpp's C51_MAXN / C51_MAXOUT
+constexpr int QR_MAX_QUANTILES = 256, QR_MAX_OUT = 4096;  // qr.hpp's QR_MAXN / QR_MAXOUT
+
+// What the host says differently for the two kinds (indexed by WideKind): the limits of N and A * N, and the
+// words of the refusals; the four whole messages are those the heads word differently beyond the noun.
+struct WideDesc {
+  const char *noun, *count, *grid;  // "the <noun> head", "<count> must be in ...", "copy of the <grid> failed"
+  int min_n, max_n, max_out;
+  const char *no_meta, *no_unit, *no_wb, *no_fused;
+};
+inline constexpr WideDesc kWide[2] = {
+    {"categorical", "num_atoms", "support", 2, C51_MAX_ATOMS, C51_MAX_OUT,
+     "the categorical head has no MGSC meta mode", "the categorical head has no unit-cotangent pass",
+     "the categorical head has no TD error to write back as a priority",
+     "the categorical head runs in gradient mode only (no fused centered RMSProp)"},
+    {"quantile", "num_quantiles", "quantiles", 1, QR_MAX_QUANTILES, QR_MAX_OUT,
+     "the quantile head takes no MGSC meta mode", "the quantile head takes no unit-cotangent pass",
+     "the quantile head takes no PER priority write-back",
+     "the quantile head takes no fused centered RMSProp (it runs in gradient mode only)"}};
+
+inline void wide_param_layout(int A, int N, int64_t off[10], int64_t sz[10], int64_t* total) {
   param_layout(A * N, 0, off, sz, total);  // leaves 0-7 are any DQN network's; fc2 is [512, A N] + [A N]
 }
-enum C51Launch { C51_LOGITS, C51_HEAD, C51_FC2_GRAD };
-
-// The quantile (QR-DQN) head in place of the scalar one (StepRequest::qr; qr.hpp): the categorical head's twin.
-// The parameter layout ends in fc2 leaves N * A wide, quantile-major (column i A + a), the step runs in gradient
-// mode, and the head's four launches, which live in the other code object, are made by qr_launch.
-struct QrHead {
-  int N;             // quantiles per action
-  const float* tau;  // [N] device, each strictly inside (0, 1)
-  float kappa;       // huber_param > 0
-  float* out;        // [2][B][A N] online(s_tm1), target(s_t)
-  float* theta;      // [B][N] online outputs of the taken action
-  float* dtheta;     // [B][N] d loss / d those outputs
-  float* dout;       // [B][A N] the dense cotangent of the online outputs
-  float* qv;         // [2][B][A] q_values
-  int32_t* astar;    // [B] argmax_a q_values of the target copy
-};
-constexpr int QR_MAX_QUANTILES = 256, QR_MAX_OUT = 4096;  // qr.hpp's QR_MAXN / QR_MAXOUT
-inline void qr_param_layout(int A, int N, int64_t off[10], int64_t sz[10], int64_t* total) {
-  param_layout(A * N, 0, off, sz, total);  // leaves 0-7 are any DQN network's; fc2 is [512, N A] + [N A]
-}
-enum QrLaunch { QR_OUTPUTS, QR_HEAD, QR_DZ1, QR_FC2_GRAD };
+enum WideLaunch { WIDE_OUTPUTS, WIDE_HEAD, WIDE_DZ1, WIDE_FC2_GRAD };
 
 // What one learner step is asked to do, set by name ({.slots = ..., .gout = ...}).  Everything left out is the
 // plain step: centered RMSProp on P->online / mu / nu over the batch `slots`.
@@ -290,20 +295,15 @@ struct StepRequest {
   const MetaSoftmax* meta_sm;  // the head forms p itself; meta_p is then its p_out
   uint8_t* xout;               // conv1 copies sample 0's s_tm1 bytes here (Conv1Src::xout)
   PhaseEvents pe;              // dqz_learner_profile: per-phase timing instead of one pass
-  // The categorical head (C51): gradient mode only, batch from `slots`; check_step words what it refuses.
-  const C51Head* c51;
-  // The quantile head (QR-DQN): as the categorical one, and never both.
-  const QrHead* qr;
+  // A wide head (C51 or QR-DQN): gradient mode only, batch from `slots`; check_step words what it refuses.
+  const WideHead* wide;
 };
 
-// One of the categorical head's three launches of a learner step (learner.hip): the logits of both copies, the
-// per-sample loss head (batch record from L->rec), the fc2 gradient into gout's fc2 leaves.
-int c51_launch(C51Launch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, void* stream);
-
-// One of the quantile head's four launches of a learner step (learner.hip): the outputs of both copies
-// (c51_logits_kernel), the per-sample loss head (batch record from L->rec; writes the dense cotangent), dz1 as a
-// batched product, the fc2 gradient into gout's fc2 leaves.
-int qr_launch(QrLaunch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, void* stream);
+// One of a wide head's launches of a learner step (learner.hip): the outputs of both copies (c51_logits_kernel,
+// generic in the output width), the per-sample loss head (batch record from L->rec; the quantile one writes the
+// dense cotangent), the quantile head's dz1 as a batched product (only with WideHead::dout), the fc2 gradient
+// into gout's fc2 leaves.
+int wide_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, void* stream);
 
 // conv1 .. fc1 forward of one network copy on n states (learner_step.hip's forward_impl, Z = 1): the fc1 split-K
 // partials are left in L->fc1p for a head of the other code object.

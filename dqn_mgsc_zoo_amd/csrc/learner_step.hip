@@ -12,11 +12,11 @@
 //     conv2 dX -> conv1 dW hand-offs, fc1 dW + fused RMSProp, conv3 / conv2
 //     dW partials                                                 bwd.hpp
 //   7 reduce of every cross-sample / split-K gradient + centered RMSProp
-// With StepRequest::c51 the categorical head's launches (c51.hpp, the other
-// code object) stand in for 4, and the fc2 gradient follows 7 in one of its own;
-// StepRequest::qr does the same with the quantile head's (qr.hpp).
+// With StepRequest::wide the launches of the categorical or the quantile head
+// (c51.hpp, qr.hpp, the other code object; wide_launch) stand in for 4, and the
+// fc2 gradient follows 7 in one of its own.
 // What a step is asked to do (batch source, gradient mode, PER write-back,
-// MGSC meta mode, the categorical head, profiling) is a StepRequest
+// MGSC meta mode, a wide head, profiling) is a StepRequest
 // (learner_impl.hpp), whose fields carry the modes' documentation; the
 // hand-off words are named in layout.hpp.
 #define DQZ_STEP_TU 1
@@ -209,30 +209,17 @@ int dqz::check_step(const dqz_learner* L, const dqz_params* P, const dqz_store* 
   if (int rc = check_store(S)) return rc;
   if (L->cfg.algo == DQZ_ALGO_PER && !r.is_weights && !r.pd) return fail(DQZ_ERR_INVALID, "PER step needs is_weights");
   if (!!r.draw + !!r.sm + !!r.smx + !!r.pd > 1) return fail(DQZ_ERR_INVALID, "a step takes at most one batch draw");
-  if (r.c51) {  // the categorical head: what it does not take, each by name
-    if (r.is_weights) return fail(DQZ_ERR_INVALID, "the categorical head takes no importance weights");
-    if (r.pd) return fail(DQZ_ERR_INVALID, "the categorical head takes no prioritized draw");
-    if (r.draw || r.sm || r.smx) return fail(DQZ_ERR_INVALID, "the categorical head takes no in-launch batch draw");
-    if (r.meta_p || r.meta_epi || r.meta_sm) return fail(DQZ_ERR_INVALID, "the categorical head has no MGSC meta mode");
-    if (r.unit) return fail(DQZ_ERR_INVALID, "the categorical head has no unit-cotangent pass");
-    if (r.wb) return fail(DQZ_ERR_INVALID, "the categorical head has no TD error to write back as a priority");
-    if (!r.gout)
-      return fail(DQZ_ERR_INVALID, "the categorical head runs in gradient mode only (no fused centered RMSProp)");
-    if (L->cfg.batch == 1) return fail(DQZ_ERR_INVALID, "the categorical head needs batch >= 2");
-    if (L->cfg.algo != DQZ_ALGO_DQN) return fail(DQZ_ERR_INVALID, "the categorical head runs on a DQN learner");
-    if (r.qr) return fail(DQZ_ERR_INVALID, "a step takes one head: the categorical or the quantile one, not both");
-  }
-  if (r.qr) {  // the quantile head: the same refusals
-    if (r.is_weights) return fail(DQZ_ERR_INVALID, "the quantile head takes no importance weights");
-    if (r.pd) return fail(DQZ_ERR_INVALID, "the quantile head takes no prioritized draw");
-    if (r.draw || r.sm || r.smx) return fail(DQZ_ERR_INVALID, "the quantile head takes no in-launch batch draw");
-    if (r.meta_p || r.meta_epi || r.meta_sm) return fail(DQZ_ERR_INVALID, "the quantile head takes no MGSC meta mode");
-    if (r.unit) return fail(DQZ_ERR_INVALID, "the quantile head takes no unit-cotangent pass");
-    if (r.wb) return fail(DQZ_ERR_INVALID, "the quantile head takes no PER priority write-back");
-    if (!r.gout)
-      return fail(DQZ_ERR_INVALID, "the quantile head takes no fused centered RMSProp (it runs in gradient mode only)");
-    if (L->cfg.batch == 1) return fail(DQZ_ERR_INVALID, "the quantile head needs batch >= 2");
-    if (L->cfg.algo != DQZ_ALGO_DQN) return fail(DQZ_ERR_INVALID, "the quantile head runs on a DQN learner");
+  if (r.wide) {  // a wide head: what it does not take, each by name (kWide words what the two say differently)
+    const WideDesc& d = kWide[r.wide->kind];
+    if (r.is_weights) return fail(DQZ_ERR_INVALID, "the %s head takes no importance weights", d.noun);
+    if (r.pd) return fail(DQZ_ERR_INVALID, "the %s head takes no prioritized draw", d.noun);
+    if (r.draw || r.sm || r.smx) return fail(DQZ_ERR_INVALID, "the %s head takes no in-launch batch draw", d.noun);
+    if (r.meta_p || r.meta_epi || r.meta_sm) return fail(DQZ_ERR_INVALID, "%s", d.no_meta);
+    if (r.unit) return fail(DQZ_ERR_INVALID, "%s", d.no_unit);
+    if (r.wb) return fail(DQZ_ERR_INVALID, "%s", d.no_wb);
+    if (!r.gout) return fail(DQZ_ERR_INVALID, "%s", d.no_fused);
+    if (L->cfg.batch == 1) return fail(DQZ_ERR_INVALID, "the %s head needs batch >= 2", d.noun);
+    if (L->cfg.algo != DQZ_ALGO_DQN) return fail(DQZ_ERR_INVALID, "the %s head runs on a DQN learner", d.noun);
   }
   return DQZ_OK;
 }
@@ -315,19 +302,14 @@ int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, c
   fb.w2 = P->online + L->off[2];
   fb.w3p = L->w3p;
   fb.w2p = L->w2p;
-  if (r.c51) {
-    // the categorical head: the logits of both copies, then the per-sample loss head (c51.hpp, the other code
-    // object); behind it the backward reads dz1 as from the scalar head
-    DQZ_PHASE(4, if (int rc = c51_launch(C51_LOGITS, L, P, r, st)) return rc);
-    DQZ_PHASE(8, if (int rc = c51_launch(C51_HEAD, L, P, r, st)) return rc);
-    DQZ_PHASE(5, hipLaunchKernelGGL(fc1_dx_kernel, dim3(fc1_dx_blocks(B)), dim3(256), 0, st, fb);
-              DQZ_HIP(hipGetLastError()));
-  } else if (r.qr) {
-    // the quantile head: the outputs of both copies, the per-sample loss head, then dz1 as a batched product over
-    // the head's dense cotangent (qr.hpp, the other code object; slot 2 is one the other steps leave at 0)
-    DQZ_PHASE(4, if (int rc = qr_launch(QR_OUTPUTS, L, P, r, st)) return rc);
-    DQZ_PHASE(8, if (int rc = qr_launch(QR_HEAD, L, P, r, st)) return rc);
-    DQZ_PHASE(2, if (int rc = qr_launch(QR_DZ1, L, P, r, st)) return rc);
+  if (r.wide) {
+    // a wide head (c51.hpp, qr.hpp, the other code object): the outputs of both copies, then the per-sample loss
+    // head, which writes dz1 itself (categorical) or a dense cotangent that a batched product turns into dz1
+    // (quantile; slot 2 is one the other steps leave at 0); behind them the backward reads dz1 as from the
+    // scalar head
+    DQZ_PHASE(4, if (int rc = wide_launch(WIDE_OUTPUTS, L, P, r, st)) return rc);
+    DQZ_PHASE(8, if (int rc = wide_launch(WIDE_HEAD, L, P, r, st)) return rc);
+    if (r.wide->dout) DQZ_PHASE(2, if (int rc = wide_launch(WIDE_DZ1, L, P, r, st)) return rc);
     DQZ_PHASE(5, hipLaunchKernelGGL(fc1_dx_kernel, dim3(fc1_dx_blocks(B)), dim3(256), 0, st, fb);
               DQZ_HIP(hipGetLastError()));
   } else if (B == 1 && !pe.on()) {
@@ -381,7 +363,7 @@ int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, c
                        : (chain ? bwd_bc_kernel<false, true> : bwd_bc_kernel<false, false>);
   DQZ_PHASE(6, hipLaunchKernelGGL(bwd, grid, dim3(256), 0, st, c3b, fb, c2b, c1dw, wbk);
             DQZ_HIP(hipGetLastError()));
-  const bool wide = r.c51 || r.qr;  // a head of the other code object owns the fc2 leaves
+  const bool wide = r.wide != nullptr;  // a head of the other code object owns the fc2 leaves
   if (pe.on() && !wide) pe.ms[7] = pe.ms[8] = 0.f;
 
   UpdArgs u{};
@@ -405,7 +387,7 @@ int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, c
   u.loss_part = L->loss_part;
   u.loss = L->loss;
   u.status = L->sync + sync_of(L).err();
-  // the categorical head owns the fc2 leaves (c51_fc2_grad_kernel below): with A = nb2 = 0 the small head
+  // a wide head owns the fc2 leaves (WIDE_FC2_GRAD below): with A = nb2 = 0 the small head
   // leaves are fc1/b alone, update_blocks counts 8 blocks for them and no range of small_grad reaches fc2
   u.A = wide ? 0 : A;
   u.B = B;
@@ -415,8 +397,7 @@ int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, c
   const unsigned nblk = update_blocks(L->sz, u.A, u.nb2);
   DQZ_PHASE(9, hipLaunchKernelGGL(update_kernel, dim3(nblk), dim3(256), 0, st, u);
             DQZ_HIP(hipGetLastError()));
-  if (r.c51) DQZ_PHASE(7, if (int rc = c51_launch(C51_FC2_GRAD, L, P, r, st)) return rc);
-  if (r.qr) DQZ_PHASE(7, if (int rc = qr_launch(QR_FC2_GRAD, L, P, r, st)) return rc);
+  if (wide) DQZ_PHASE(7, if (int rc = wide_launch(WIDE_FC2_GRAD, L, P, r, st)) return rc);
   return DQZ_OK;
 }
 

@@ -184,10 +184,13 @@ class Learner:
     _native.check(create(ctypes.byref(ocfg), *layout_args, ctypes.byref(oh)))
     return oh
 
+  def _entry(self, entry):
+    """The head's own `entry` (_ENTRIES) of the library."""
+    return getattr(_native.lib(), self._ENTRIES[entry])
+
   def _call(self, entry, *args):
-    """The head's own `entry` (_ENTRIES) on the handle that owns the state."""
-    fn = getattr(_native.lib(), self._ENTRIES[entry])
-    return fn(getattr(self, self._OWNER), *args)
+    """That entry on the handle that owns the state."""
+    return self._entry(entry)(getattr(self, self._OWNER), *args)
 
   def __del__(self):
     if _native is None or _native._lib is None:  # pylint: disable=protected-access
@@ -548,121 +551,169 @@ def sample_uniform(base, size, capacity, n, seed, counter, out, stream=None):
   return out
 
 
-class C51Learner(Learner):
-  """The categorical (C51) learner: `update` of c51/agent.py:109-117 and
-  `select_action` of :121-129 on device (dqz_c51_*).
+def _wide_entries(prefix):
+  """_ENTRIES of a wide head: every entry is `prefix` + its own name."""
+  return {e: prefix + e for e in (
+      'create', 'learner', 'optimizer_create', 'destroy', 'step', 'grad',
+      'outputs', 'debug', 'profile', 'forward', 'forward_slots', 'act')}
+
+
+class _WideLearner(Learner):
+  """What the categorical and the quantile learners share: everything but the
+  names a subclass states below.
 
   Same state surface as `Learner` (params, moments, opt_state, sync_target,
-  sync_status, grad_norm); the step is the learner step with the categorical
-  head, in gradient mode, followed by the optimizer, so the optimizer is Adam
-  or plain RMSProp, alone or behind clip_by_global_norm (the reference's chain,
-  c51/run_atari.py:210-216, is the default)."""
+  sync_status, grad_norm); the step is the learner step with the wide head, in
+  gradient mode, followed by the optimizer, so the optimizer is Adam or plain
+  RMSProp, alone or behind clip_by_global_norm (the reference's chain is the
+  default)."""
 
-  _c51 = None  # dqz_c51 handle; it owns the dqz_learner behind _h
-  _OWNER = '_c51'
-  _ENTRIES = dict(destroy='dqz_c51_destroy', forward='dqz_c51_forward',
-                  forward_slots='dqz_c51_forward_slots', act='dqz_c51_act')
+  _wide = None  # the head's handle (dqz_c51 / dqz_qr); it owns the dqz_learner behind _h
+  _OWNER = '_wide'
+  # what a subclass states
+  _CLASS = _NETWORK = None  # its own name and its network factory's, for messages
+  _SPEC = None  # the network spec's class ...
+  _COUNT = _GRID = None  # ... and its attributes: N and the [N] grid (also the learner's tensor of it)
+  _TAKEN = None  # the learner's [B,N] output tensor of the taken action
+  _LEARNING_RATE = None  # of the default optimizer
+  _ALGO = _TITLE = _HEAD = None  # `algo`, and the head's names in messages
+  _PROFILE_SLOTS = None  # profile(): phase slot -> the head's launch there
 
-  def __init__(self, network: networks_lib.C51NetworkSpec, batch_size,
-               optimizer=None, device='cuda'):
-    if not isinstance(network, networks_lib.C51NetworkSpec):
-      raise ValueError('C51Learner needs networks.c51_atari_network')
+  def __init__(self, network, batch_size, optimizer, device, *head_args):
+    if not isinstance(network, self._SPEC):
+      raise ValueError('%s needs networks.%s' % (self._CLASS, self._NETWORK))
+    head_args = self._check_head_args(*head_args)
     optimizer = optimizer or chain(clip_by_global_norm(10.0),
-                                   adam(2.5e-4, eps=0.01 / 32))
+                                   adam(self._LEARNING_RATE, eps=0.01 / 32))
     if is_centered_rmsprop(optimizer):
       raise NotImplementedError(
-          'C51Learner applies its optimizer to the finished gradient: centered '
+          '%s applies its optimizer to the finished gradient: centered '
           'RMSProp exists only fused into the DQN step; use adam(...), '
           'rmsprop(..., centered=False) or chain(clip_by_global_norm(c), one '
-          'of them)')
-    self.algo = 'c51'
+          'of them)' % self._CLASS)
+    self.algo = self._ALGO
     self.grad_error_bound = 0.0
     self._alloc_state(network, batch_size, optimizer, device)
-    b, a, n = self.batch_size, network.num_actions, network.num_atoms
+    b, a, n = self.batch_size, network.num_actions, getattr(network, self._COUNT)
     f32 = dict(dtype=torch.float32, device=self.device)
-    self.support = torch.from_numpy(network.support).to(self.device)
-    self.logits_a = torch.zeros((b, n), **f32)
+    grid = torch.from_numpy(getattr(network, self._GRID)).to(self.device)
+    setattr(self, self._GRID, grid)
+    setattr(self, self._TAKEN, torch.zeros((b, n), **f32))
     self.q = torch.zeros((2, b, a), **f32)
     self.loss_b = torch.zeros((b,), **f32)
     self.loss = torch.zeros((1,), **f32)
     self.a_star = torch.zeros((b,), dtype=torch.int32, device=self.device)
-    lib = _native.lib()
     handle = ctypes.c_void_p()
-    _native.check(lib.dqz_c51_create(
+    _native.check(self._entry('create')(
         ctypes.byref(self._learner_config(_native.ALGO_DQN)), n,
-        _native.ptr(self.support), ctypes.byref(handle)))
-    self._c51 = handle
+        _native.ptr(grid), *head_args, ctypes.byref(handle)))
+    self._wide = handle
     inner = ctypes.c_void_p()
-    _native.check(lib.dqz_c51_learner(handle, ctypes.byref(inner)))
-    self._h = inner  # owned by the c51 handle: sync_status, fetch_activations
-    self._opt_h = self._create_optimizer(lib.dqz_c51_optimizer_create, n)
+    _native.check(self._call('learner', ctypes.byref(inner)))
+    self._h = inner  # owned by the head's handle: sync_status, fetch_activations
+    self._opt_h = self._create_optimizer(self._entry('optimizer_create'), n)
+
+  def _check_head_args(self):
+    """The head's own constructor arguments, checked: what its create entry
+    takes between the grid and the handle."""
+    return ()
+
+  def _out_shape(self, b, a, n):
+    """fetch_head's view of one copy's [B][A N] outputs."""
+    raise NotImplementedError
 
   def load_opt_state(self, state):
     """Restores what opt_state() returned; a centered-RMSProp state (a DQN
     agent's checkpoint) is refused by name."""
     if optim_state.is_rmsprop_state(state):
       raise ValueError(
-          'a centered-RMSProp state cannot restore a C51 learner (its '
-          'optimizer is %s)' % type(self.base_optimizer).__name__)
+          'a centered-RMSProp state cannot restore a %s learner (its '
+          'optimizer is %s)' % (self._TITLE, type(self.base_optimizer).__name__))
     super().load_opt_state(state)
 
   def step(self, store, slots, stream=None):  # pylint: disable=arguments-differ
     """One learner step on replay `slots` (device int32 [B])."""
     self._check_slots(slots)
-    _native.check(_native.lib().dqz_c51_step(
-        self._c51, ctypes.byref(self._params_c), store.c_ref(),
-        _native.ptr(slots), self._opt_h, _native.ptr(self.count),
-        _native.stream_handle(stream)))
+    _native.check(self._call(
+        'step', ctypes.byref(self._params_c), store.c_ref(), _native.ptr(slots),
+        self._opt_h, _native.ptr(self.count), _native.stream_handle(stream)))
 
   def grad(self, store, slots, out=None, stream=None):  # pylint: disable=arguments-differ
     """jax.grad(loss_fn) of the same step into a flat tensor (no update)."""
     self._check_slots(slots)
     out = torch.zeros_like(self.online) if out is None else out
-    _native.check(_native.lib().dqz_c51_grad(
-        self._c51, ctypes.byref(self._params_c), store.c_ref(),
-        _native.ptr(slots), _native.ptr(out), _native.stream_handle(stream)))
+    _native.check(self._call(
+        'grad', ctypes.byref(self._params_c), store.c_ref(), _native.ptr(slots),
+        _native.ptr(out), _native.stream_handle(stream)))
     return out
 
   def fetch_outputs(self, stream=None):
-    """(logits of the taken action [B,N], q_values [2,B,A] of online(s_tm1)
+    """(outputs of the taken action [B,N], q_values [2,B,A] of online(s_tm1)
     and target(s_t), per-sample loss [B], mean loss [1], the target's greedy
     action [B]) of the last step, copied into self tensors."""
-    _native.check(_native.lib().dqz_c51_outputs(
-        self._c51, _native.ptr(self.logits_a), _native.ptr(self.q),
+    taken = getattr(self, self._TAKEN)
+    _native.check(self._call(
+        'outputs', _native.ptr(taken), _native.ptr(self.q),
         _native.ptr(self.loss_b), _native.ptr(self.loss),
         _native.ptr(self.a_star), _native.stream_handle(stream)))
-    return self.logits_a, self.q, self.loss_b, self.loss, self.a_star
+    return taken, self.q, self.loss_b, self.loss, self.a_star
 
   def fetch_head(self, stream=None):
-    """Diagnostic: the last step's q_logits [2,B,A,N] and dlogits [B,N]."""
-    b, a, n = self.batch_size, self.network.num_actions, self.network.num_atoms
-    logits = torch.empty((2, b, a, n), dtype=torch.float32, device=self.device)
-    dlogits = torch.empty((b, n), dtype=torch.float32, device=self.device)
-    _native.check(_native.lib().dqz_c51_debug(
-        self._c51, _native.ptr(logits), _native.ptr(dlogits),
-        _native.stream_handle(stream)))
-    return logits, dlogits
+    """Diagnostic: the last step's outputs of both copies (_out_shape) and
+    the cotangent [B,N] of the taken action's."""
+    b, a = self.batch_size, self.network.num_actions
+    n = getattr(self.network, self._COUNT)
+    out = torch.empty(self._out_shape(b, a, n), dtype=torch.float32,
+                      device=self.device)
+    dtaken = torch.empty((b, n), dtype=torch.float32, device=self.device)
+    _native.check(self._call('debug', _native.ptr(out), _native.ptr(dtaken),
+                             _native.stream_handle(stream)))
+    return out, dtaken
 
   def profile(self, store, slots, iters=20, stream=None):  # pylint: disable=arguments-differ
-    """Average ms per launch (dqz_c51_profile), dict; the gradient goes to a
-    scratch tensor and no parameter changes."""
+    """Average ms per launch (the head's profile entry), dict; the gradient
+    goes to a scratch tensor and no parameter changes."""
     self._check_slots(slots)
     out = (ctypes.c_float * _native.NUM_PHASES)()
     scratch = torch.zeros_like(self.online)
-    _native.check(_native.lib().dqz_c51_profile(
-        self._c51, ctypes.byref(self._params_c), store.c_ref(),
+    _native.check(self._call(
+        'profile', ctypes.byref(self._params_c), store.c_ref(),
         _native.ptr(slots), _native.ptr(scratch), int(iters), out,
         _native.stream_handle(stream)))
     names = list(_native.PHASE_NAMES)
-    names[4], names[8], names[7] = 'c51_logits', 'c51_head', 'c51_fc2_grad'
+    for slot, name in self._PROFILE_SLOTS.items():
+      names[slot] = name
     return {n: float(t) for n, t in zip(names, out) if t > 0.0}
 
   def _no_fused_draw(self, *unused_args, **unused_kwargs):
     raise NotImplementedError(
-        'the categorical step takes its batch as slots: sample them first '
-        '(replay.sample_slots) and call step')
+        'the %s step takes its batch as slots: sample them first '
+        '(replay.sample_slots) and call step' % self._HEAD)
 
   step_uniform = step_logits = step_per_draw = _no_fused_draw
+
+
+class C51Learner(_WideLearner):
+  """The categorical (C51) learner: `update` of c51/agent.py:109-117 and
+  `select_action` of :121-129 on device (dqz_c51_*); the default optimizer is
+  the chain of c51/run_atari.py:210-216.  Its tensors of the head: `support`
+  [N] and `logits_a` [B,N]."""
+
+  _ENTRIES = _wide_entries('dqz_c51_')
+  _CLASS, _NETWORK = 'C51Learner', 'c51_atari_network'
+  _SPEC = networks_lib.C51NetworkSpec
+  _COUNT, _GRID, _TAKEN = 'num_atoms', 'support', 'logits_a'
+  _LEARNING_RATE = 2.5e-4
+  _ALGO, _TITLE, _HEAD = 'c51', 'C51', 'categorical'
+  _PROFILE_SLOTS = {4: 'c51_logits', 8: 'c51_head', 7: 'c51_fc2_grad'}
+  _c51 = property(lambda self: self._wide)
+
+  def __init__(self, network: networks_lib.C51NetworkSpec, batch_size,
+               optimizer=None, device='cuda'):
+    super().__init__(network, batch_size, optimizer, device)
+
+  def _out_shape(self, b, a, n):
+    return (2, b, a, n)  # q_logits
 
 
 def check_huber_param(huber_param):
@@ -678,123 +729,32 @@ def check_huber_param(huber_param):
   return huber_param
 
 
-class QrLearner(Learner):
+class QrLearner(_WideLearner):
   """The quantile (QR-DQN) learner: `update` of qrdqn/agent.py:112-120 and
-  `select_action` of :122-134 on device (dqz_qr_*).
+  `select_action` of :122-134 on device (dqz_qr_*); the default optimizer is
+  the chain of qrdqn/run_atari.py:213-219.  Its tensors of the head:
+  `quantiles` [N] and `theta` [B,N]."""
 
-  Same state surface as `Learner` (params, moments, opt_state, sync_target,
-  sync_status, grad_norm); the step is the learner step with the quantile
-  head, in gradient mode, followed by the optimizer, so the optimizer is Adam
-  or plain RMSProp, alone or behind clip_by_global_norm (the reference's chain,
-  qrdqn/run_atari.py:213-219, is the default)."""
-
-  _qr = None  # dqz_qr handle; it owns the dqz_learner behind _h
-  _OWNER = '_qr'
-  _ENTRIES = dict(destroy='dqz_qr_destroy', forward='dqz_qr_forward',
-                  forward_slots='dqz_qr_forward_slots', act='dqz_qr_act')
+  _ENTRIES = _wide_entries('dqz_qr_')
+  _CLASS, _NETWORK = 'QrLearner', 'qr_atari_network'
+  _SPEC = networks_lib.QRNetworkSpec
+  _COUNT, _GRID, _TAKEN = 'num_quantiles', 'quantiles', 'theta'
+  _LEARNING_RATE = 5e-5
+  _ALGO, _TITLE, _HEAD = 'qrdqn', 'QR-DQN', 'quantile'
+  _PROFILE_SLOTS = {4: 'qr_outputs', 8: 'qr_head', 2: 'qr_dz1',
+                    7: 'qr_fc2_grad'}
+  _qr = property(lambda self: self._wide)
 
   def __init__(self, network: networks_lib.QRNetworkSpec, batch_size,
                huber_param=1.0, optimizer=None, device='cuda'):
-    if not isinstance(network, networks_lib.QRNetworkSpec):
-      raise ValueError('QrLearner needs networks.qr_atari_network')
+    super().__init__(network, batch_size, optimizer, device, huber_param)
+
+  def _check_head_args(self, huber_param):  # pylint: disable=arguments-differ
     self.huber_param = check_huber_param(huber_param)
-    optimizer = optimizer or chain(clip_by_global_norm(10.0),
-                                   adam(5e-5, eps=0.01 / 32))
-    if is_centered_rmsprop(optimizer):
-      raise NotImplementedError(
-          'QrLearner applies its optimizer to the finished gradient: centered '
-          'RMSProp exists only fused into the DQN step; use adam(...), '
-          'rmsprop(..., centered=False) or chain(clip_by_global_norm(c), one '
-          'of them)')
-    self.algo = 'qrdqn'
-    self.grad_error_bound = 0.0
-    self._alloc_state(network, batch_size, optimizer, device)
-    b, a, n = self.batch_size, network.num_actions, network.num_quantiles
-    f32 = dict(dtype=torch.float32, device=self.device)
-    self.quantiles = torch.from_numpy(network.quantiles).to(self.device)
-    self.theta = torch.zeros((b, n), **f32)
-    self.q = torch.zeros((2, b, a), **f32)
-    self.loss_b = torch.zeros((b,), **f32)
-    self.loss = torch.zeros((1,), **f32)
-    self.a_star = torch.zeros((b,), dtype=torch.int32, device=self.device)
-    lib = _native.lib()
-    handle = ctypes.c_void_p()
-    _native.check(lib.dqz_qr_create(
-        ctypes.byref(self._learner_config(_native.ALGO_DQN)), n,
-        _native.ptr(self.quantiles), self.huber_param, ctypes.byref(handle)))
-    self._qr = handle
-    inner = ctypes.c_void_p()
-    _native.check(lib.dqz_qr_learner(handle, ctypes.byref(inner)))
-    self._h = inner  # owned by the qr handle: sync_status, fetch_activations
-    self._opt_h = self._create_optimizer(lib.dqz_qr_optimizer_create, n)
+    return (self.huber_param,)
 
-  def load_opt_state(self, state):
-    """Restores what opt_state() returned; a centered-RMSProp state (a DQN
-    agent's checkpoint) is refused by name."""
-    if optim_state.is_rmsprop_state(state):
-      raise ValueError(
-          'a centered-RMSProp state cannot restore a QR-DQN learner (its '
-          'optimizer is %s)' % type(self.base_optimizer).__name__)
-    super().load_opt_state(state)
-
-  def step(self, store, slots, stream=None):  # pylint: disable=arguments-differ
-    """One learner step on replay `slots` (device int32 [B])."""
-    self._check_slots(slots)
-    _native.check(_native.lib().dqz_qr_step(
-        self._qr, ctypes.byref(self._params_c), store.c_ref(),
-        _native.ptr(slots), self._opt_h, _native.ptr(self.count),
-        _native.stream_handle(stream)))
-
-  def grad(self, store, slots, out=None, stream=None):  # pylint: disable=arguments-differ
-    """jax.grad(loss_fn) of the same step into a flat tensor (no update)."""
-    self._check_slots(slots)
-    out = torch.zeros_like(self.online) if out is None else out
-    _native.check(_native.lib().dqz_qr_grad(
-        self._qr, ctypes.byref(self._params_c), store.c_ref(),
-        _native.ptr(slots), _native.ptr(out), _native.stream_handle(stream)))
-    return out
-
-  def fetch_outputs(self, stream=None):
-    """(outputs of the taken action theta [B,N], q_values [2,B,A] of
-    online(s_tm1) and target(s_t), per-sample loss [B], mean loss [1], the
-    target's greedy action [B]) of the last step, copied into self tensors."""
-    _native.check(_native.lib().dqz_qr_outputs(
-        self._qr, _native.ptr(self.theta), _native.ptr(self.q),
-        _native.ptr(self.loss_b), _native.ptr(self.loss),
-        _native.ptr(self.a_star), _native.stream_handle(stream)))
-    return self.theta, self.q, self.loss_b, self.loss, self.a_star
-
-  def fetch_head(self, stream=None):
-    """Diagnostic: the last step's q_dist [2,B,N,A] and dtheta [B,N]."""
-    b, a, n = self.batch_size, self.network.num_actions, self.network.num_quantiles
-    q_dist = torch.empty((2, b, n, a), dtype=torch.float32, device=self.device)
-    dtheta = torch.empty((b, n), dtype=torch.float32, device=self.device)
-    _native.check(_native.lib().dqz_qr_debug(
-        self._qr, _native.ptr(q_dist), _native.ptr(dtheta),
-        _native.stream_handle(stream)))
-    return q_dist, dtheta
-
-  def profile(self, store, slots, iters=20, stream=None):  # pylint: disable=arguments-differ
-    """Average ms per launch (dqz_qr_profile), dict; the gradient goes to a
-    scratch tensor and no parameter changes."""
-    self._check_slots(slots)
-    out = (ctypes.c_float * _native.NUM_PHASES)()
-    scratch = torch.zeros_like(self.online)
-    _native.check(_native.lib().dqz_qr_profile(
-        self._qr, ctypes.byref(self._params_c), store.c_ref(),
-        _native.ptr(slots), _native.ptr(scratch), int(iters), out,
-        _native.stream_handle(stream)))
-    names = list(_native.PHASE_NAMES)
-    names[4], names[8], names[2], names[7] = (
-        'qr_outputs', 'qr_head', 'qr_dz1', 'qr_fc2_grad')
-    return {n: float(t) for n, t in zip(names, out) if t > 0.0}
-
-  def _no_fused_draw(self, *unused_args, **unused_kwargs):
-    raise NotImplementedError(
-        'the quantile step takes its batch as slots: sample them first '
-        '(replay.sample_slots) and call step')
-
-  step_uniform = step_logits = step_per_draw = _no_fused_draw
+  def _out_shape(self, b, a, n):
+    return (2, b, n, a)  # q_dist: quantile-major
 
 
 class _BorrowedLearner:

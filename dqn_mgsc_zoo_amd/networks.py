@@ -158,12 +158,28 @@ def double_dqn_atari_network(num_actions: int) -> NetworkSpec:
   return NetworkSpec(num_actions=int(num_actions), shared_bias=True)
 
 
+class WideNetworkSpec(NetworkSpec):
+  """What the categorical and the quantile networks share: `linear_1` is
+  [512, A * N] wide, N being the attribute a subclass names in `_COUNT`, and
+  the device layout is its own entry's (`_LAYOUT`, which also holds N to the
+  head's limits)."""
+  _COUNT = None
+  _LAYOUT = None
+
+  def leaf_shapes(self):
+    outputs = self.num_actions * getattr(self, self._COUNT)
+    return [shape_fn(outputs) for _, _, shape_fn, _ in _LEAVES]
+
+  def layout(self):
+    return self._LAYOUT(self.num_actions, getattr(self, self._COUNT))
+
+
 class C51NetworkOutputs(typing.NamedTuple):
   q_logits: typing.Any
   q_values: typing.Any
 
 
-class C51NetworkSpec(NetworkSpec):
+class C51NetworkSpec(WideNetworkSpec):
   """NetworkSpec of the categorical network: `dqn_atari_network`'s leaf names
   with `linear_1` [512, A * N] wide, plus the fixed support (float32 [N],
   strictly increasing) and its length `num_atoms`.
@@ -180,12 +196,8 @@ class C51NetworkSpec(NetworkSpec):
     self.num_atoms = int(support.size)
     return self
 
-  def leaf_shapes(self):
-    outputs = self.num_actions * self.num_atoms
-    return [shape_fn(outputs) for _, _, shape_fn, _ in _LEAVES]
-
-  def layout(self):
-    return _native.c51_param_layout(self.num_actions, self.num_atoms)
+  _COUNT = 'num_atoms'
+  _LAYOUT = staticmethod(_native.c51_param_layout)
 
 
 def c51_atari_network(num_actions: int, support) -> C51NetworkSpec:
@@ -198,7 +210,7 @@ class QRNetworkOutputs(typing.NamedTuple):
   q_dist: typing.Any
 
 
-class QRNetworkSpec(NetworkSpec):
+class QRNetworkSpec(WideNetworkSpec):
   """NetworkSpec of the quantile network: `dqn_atari_network`'s leaf names
   with `linear_1` [512, N * A] wide, plus the fixed `quantiles` (float32 [N],
   each strictly inside (0, 1)) and their number `num_quantiles`.
@@ -217,12 +229,8 @@ class QRNetworkSpec(NetworkSpec):
     self.num_quantiles = int(quantiles.size)
     return self
 
-  def leaf_shapes(self):
-    outputs = self.num_actions * self.num_quantiles
-    return [shape_fn(outputs) for _, _, shape_fn, _ in _LEAVES]
-
-  def layout(self):
-    return _native.qr_param_layout(self.num_actions, self.num_quantiles)
+  _COUNT = 'num_quantiles'
+  _LAYOUT = staticmethod(_native.qr_param_layout)
 
 
 def qr_atari_network(num_actions: int, quantiles) -> QRNetworkSpec:

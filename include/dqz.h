@@ -778,7 +778,9 @@ int dqz_qr_optimizer_create(const dqz_optimizer_config* cfg, int num_quantiles, 
 
 typedef struct dqz_qr dqz_qr;
 
-/* A learner on the quantile layout plus the head's buffers.  cfg: batch
+/* A learner on the quantile layout plus the head's buffers (one implementation
+ * stands behind this handle type and dqz_c51; the two types keep a handle of
+ * one kind out of the other's entries).  cfg: batch
  * 2..256, num_actions, algo DQZ_ALGO_DQN; its optimizer fields and
  * grad_error_bound are unused.  quantiles: device f32 [num_quantiles], copied
  * and checked on the host (this call synchronises): each finite and strictly

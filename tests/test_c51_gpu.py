@@ -371,6 +371,26 @@ def test_a_step_is_its_gradient_then_apply(device, optimizer):
     assert lrn.sync_status() == 0
 
 
+def test_profile_names_the_heads_launches(device):
+  """C51Learner.profile reports the step's own launches and the categorical
+  head's three under their names, nothing in slot 2 (the quantile head's dz1
+  product, which this step does not issue), and changes no state."""
+  case = _case(5, 3, 7)
+  lrn, st = _device(case, device)
+  slots = torch.from_numpy(case['slots']).to(device)
+  state = (lrn.online, lrn.target, lrn.mu, lrn.nu, lrn.count)
+  before = [t.clone() for t in state]
+  ms = lrn.profile(st, slots, iters=2)
+  torch.cuda.synchronize()
+  print(sorted(ms))
+  assert set(ms) == {
+      'conv1_fwd', 'fc1_fwd', 'fc1_dx',
+      'conv3_dx+conv2_dx+fc1_dw+conv3_dw+conv2_dw+conv1_dw', 'update',
+      'c51_logits', 'c51_head', 'c51_fc2_grad'}
+  for t, b in zip(state, before):
+    assert np.array_equal(_bits(t), _bits(b))
+
+
 def test_three_captured_steps_equal_three_eager_steps(device):
   case = _case(8, 6, 51)
   lrn, st = _device(case, device)
