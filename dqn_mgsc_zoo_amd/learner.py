@@ -362,7 +362,10 @@ class Learner:
         _native.stream_handle(stream)))
 
   def grad(self, store, slots, weights=None, out=None, stream=None):
-    """jax.grad(loss_fn) of the same step into a flat tensor (no update)."""
+    """jax.grad(loss_fn) of the same step into a flat tensor (no update).
+    Every element of every leaf is written; the padding floats between the
+    leaves and behind the last keep what `out` held (zeros in the tensor
+    allocated here)."""
     self._check_slots(slots)
     out = torch.zeros_like(self.online) if out is None else out
     _native.check(_native.lib().dqz_learner_grad(
@@ -639,7 +642,10 @@ class _WideLearner(Learner):
         self._opt_h, _native.ptr(self.count), _native.stream_handle(stream)))
 
   def grad(self, store, slots, out=None, stream=None):  # pylint: disable=arguments-differ
-    """jax.grad(loss_fn) of the same step into a flat tensor (no update)."""
+    """jax.grad(loss_fn) of the same step into a flat tensor (no update).
+    Every element of every leaf is written; the padding floats between the
+    leaves and behind the last keep what `out` held (zeros in the tensor
+    allocated here)."""
     self._check_slots(slots)
     out = torch.zeros_like(self.online) if out is None else out
     _native.check(self._call(

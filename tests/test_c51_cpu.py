@@ -208,6 +208,10 @@ def _refusals():
       ('create-too-wide', create(_cfg(num_actions=18), 57), 'num_actions * num_atoms must be <= 1024'),
       ('create-no-actions', create(_cfg(num_actions=0), 51), 'num_actions must be in [1, 32]'),
       ('create-batch-one', create(_cfg(batch=1), 51), 'batch must be in [2, 256]'),
+      # the first value past each limit (N = 65 and batch 1 are above)
+      ('create-a-n-1025', create(_cfg(num_actions=25), 41), 'num_actions * num_atoms must be <= 1024'),
+      ('create-33-actions', create(_cfg(num_actions=33), 31), 'num_actions must be in [1, 32]'),
+      ('create-batch-257', create(_cfg(batch=257), 51), 'batch must be in [2, 256]'),
       ('create-double-q', create(_cfg(algo=1), 51), 'the categorical head runs on a DQN learner'),
       ('layout-one-atom', layout(6, 1), 'num_atoms must be in [2, 64]'),
       ('layout-too-wide', layout(32, 33), 'num_actions * num_atoms must be <= 1024'),
@@ -304,3 +308,31 @@ def test_network_spec_surface(lib):
     networks.c51_atari_network(6, [0.0, 1.0, 1.0])
   with pytest.raises(ValueError, match='num_atoms < 2'):
     networks.c51_atari_network(6, [0.0])
+
+
+# -- the input conditions of the GPU tests' corner shapes, without a GPU ---------
+
+def _corner_ids():
+  from tests import test_c51_gpu as gpu  # pylint: disable=g-import-not-at-top
+  return gpu.CORNERS
+
+
+@pytest.mark.parametrize('shape', _corner_ids(), ids=lambda s: '%dx%dx%d' % s)
+def test_corner_shapes_meet_their_input_conditions(lib, shape):
+  """tests/test_c51_gpu.py's _check_conditions on each corner shape's pinned
+  seed, in float64 on the CPU: every condition but the ones WAIVED names for
+  that shape, and each waiver is one the shape makes impossible (or, for the
+  kink-free draw, one its tests do not need)."""
+  from tests import test_c51_gpu as gpu  # pylint: disable=g-import-not-at-top
+  b, a, n = shape
+  case = gpu._case(*shape)  # pylint: disable=protected-access
+  gpu._check_conditions(case)  # pylint: disable=protected-access
+  waived = gpu.WAIVED.get(shape, set())
+  assert ('absent action' in waived) == (a == 1) and ('margin' in waived) == (a == 1)
+  assert ('kink-free draw' in waived) == (shape in gpu.STAGE_ONLY)
+  assert waived <= {'absent action', 'margin', 'kink-free draw'}
+  assert len(case['slots']) == b and case['slots'][0] == gpu.SPECIAL
+  if shape not in gpu.STAGE_ONLY:  # the end-to-end step's batch is kink-free
+    s = helpers.stacks_from(case['host']['frames'], case['host']['fidx'], case['slots'], 0)
+    assert learner_ref.relu_margin(case['online'], s) >= 1e-6
+  assert a * n <= 1024 and 2 <= n <= 64 and 1 <= a <= 32 and 2 <= b <= 256

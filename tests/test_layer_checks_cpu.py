@@ -77,3 +77,87 @@ def test_a_two_piece_weight_split_breaks_the_rms_bar(net_and_batch):
   print('%s with two-piece weights: max err / bound %.3f, rms / sequential rms %.0f' % (
       name, r['max_over_bound'], r['rms_ratio']))
   assert r['ok_bound'] and not r['ok_rms'] and r['rms_ratio'] > 5 * lc.RMS_MARGIN  # measured 41
+
+
+# -- the sample subset and K in pieces (the large batches of tests/test_layers_gpu.py) --
+
+NEW_BATCHES = (4, 8, 6, 17, 65, 129, 256)
+
+
+@pytest.mark.parametrize('batch', NEW_BATCHES)
+def test_the_subset_holds_the_boundary_samples(batch):
+  got = lc.boundary_samples(batch)
+  assert list(got) == sorted(set(got)) and got[0] == 0 and got[-1] == batch - 1
+  for m in (16, 32, 48, 64, 128):  # both sides of each, where the batch has them
+    for s in (m - 1, m):
+      assert (s in got) == (s < batch), (batch, s)
+  assert len(got) <= 12
+  sel = lc.sample_subset(batch)
+  if batch <= lc.SUBSET_ABOVE:
+    assert np.array_equal(sel, np.arange(batch))
+  else:
+    assert np.array_equal(sel, got)
+
+
+def test_take_samples_cuts_sample_major_rows():
+  arr = np.arange(5 * 3 * 2).reshape(15, 2)  # 5 samples x 3 rows
+  assert np.array_equal(lc.take_samples(arr, 5, [0, 4]), np.concatenate([arr[:3], arr[12:]]))
+  per_sample = np.arange(5 * 4).reshape(5, 2, 2)
+  assert np.array_equal(lc.take_samples(per_sample, 5, [1, 3]), per_sample[[1, 3]])
+
+
+def test_a_product_damaged_in_a_selected_sample_fails(net_and_batch):
+  """conv2 of a 65-sample batch (one input tiled: the products are what
+  matters), checked on the subset as tests/test_layers_gpu.py does: damage
+  inside a selected sample fails both ways of damaging, the clean product
+  passes."""
+  params, _, cache = net_and_batch
+  batch = 65
+  y1 = np.tile(cache['y0'][:1].astype(np.float32), (batch, 1, 1, 1))
+  y1 *= np.linspace(0.5, 1.5, batch, dtype=np.float32)[:, None, None, None]  # no two samples alike
+  name = learner_ref.CONV_NAMES[1]
+  w, b = params[name]['w'].reshape(-1, 64), params[name]['b']
+  full = (lc.conv_cols(y1, 1).astype(np.float32) @ w + b).reshape(batch, 9, 9, 64)
+  sel = lc.sample_subset(batch)
+  assert 64 in sel and 63 in sel and 40 not in sel
+
+  def check(got):
+    return lc.product_check(lc.take_samples(got, batch, sel), lc.conv_cols(lc.take_samples(y1, batch, sel), 1), w, b)
+
+  r = check(full)
+  assert r['ok_bound'] and r['ok_rms']
+  for s in (0, 15, 16, 63, 64):  # one element of one selected sample, off by 1e-3 of its size
+    bad = full.copy()
+    bad[s, 4, 4, 7] += 1e-3 * max(abs(bad[s, 4, 4, 7]), 1.0)
+    assert not check(bad)['ok_bound'], s
+  bad = full.copy()  # sample 64 computed from sample 63's input: a row-group tail read one row low
+  bad[64] = full[63]
+  assert not check(bad)['ok_bound']
+
+
+def test_chunked_sequential_product_is_the_unchunked_one_bit_for_bit():
+  rng = np.random.default_rng(9)
+  a = rng.standard_normal((37, 403)).astype(np.float32)
+  w = rng.standard_normal((403, 11)).astype(np.float32)
+  b = rng.standard_normal(11).astype(np.float32)
+  whole = lc.seq_f32(a, w, b)
+  cuts = [0, 1, 64, 65, 200, 403]  # uneven pieces, one of a single term
+  acc = None
+  for lo, hi in zip(cuts[:-1], cuts[1:]):
+    acc = lc.seq_f32(a[:, lo:hi], w[lo:hi], b, acc=acc, last=hi == 403)
+  assert np.array_equal(acc.view(np.uint32), whole.view(np.uint32))
+  # and through product_check: the same bars from the pieces as from the whole
+  got = a @ w + b
+  one = lc.product_check(got, a, w, b)
+  blocks = lc.product_check(got, [a[:, lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:])],
+                            [w[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:])], b)
+  pairs = lc.product_check(got, ((a[:, lo:hi], w[lo:hi]) for lo, hi in zip(cuts[:-1], cuts[1:])), None, b)
+  for r in (blocks, pairs):
+    # (the fp64 reference adds its pieces in another order: 1e-16 of the values, 1e-10 of an error of 1e-6)
+    assert abs(r['rms_seq'] - one['rms_seq']) <= 1e-8 * one['rms_seq']
+    assert r['ok_bound'] and r['ok_rms']
+    assert abs(r['max_over_bound'] - one['max_over_bound']) <= 1e-6
+  # a term dropped from one piece is seen
+  short = a.copy()
+  short[:, 200] = 0
+  assert not lc.product_check(short @ w + b, [a[:, :200], a[:, 200:]], [w[:200], w[200:]], b)['ok_bound']

@@ -34,6 +34,36 @@ exists to see what a (K + 3) bound with K in the hundreds cannot; with K <=
   ('double', 5, 6)   Z = 3, shared bias, 8-job path, a partial 32-row group
   ('dqn', 32, 6)     the workload's own shape
   ('per', 40, 18)    second row group partial; 18 actions; IS weights
+
+and at the corners of what dqz_learner_create accepts (batch 1 .. MAXB = 256,
+1 .. MAXA = 32 actions), each on a limit or on the first shape past a switch:
+
+  ('dqn', 4, 1)      the last fc1_gemv_kernel batch, all four of its rows live;
+                     A = 1: max and argmax over one action, fc2 K = Z A = 2
+  ('dqn', 8, 8)      Z B = 16, the last 8-job forward (fwd_conv_jobs); Z A = 16,
+                     the last T = 32 reduction of head_body (lgT); the last A
+                     of launch_head_z's AMAX = 8 instantiation
+  ('double', 6, 8)   Z B = 18, the first 4-job forward; Z A = 24, T = 16 inside
+                     AMAX = 8; shared bias
+  ('per', 17, 9)     the first A on the MAXA instantiation; one row past a
+                     16-row group; conv1 slabs 4 B = 68, the first
+                     sum_split2_r<2> of sum_slabs
+  ('double', 65, 32) the first batch off the chain grid (BWD_CHAIN_MAXB = 64);
+                     conv2 / conv3 slabs 65, their first sum_split2_r<2>; A = 32
+                     with Z = 3: all 96 q threads and every s_red column live;
+                     conv1 slabs 260, the loop form with a tail
+  ('dqn', 129, 32)   conv2 / conv3 slabs 129, their first loop form; 32
+                     separate fc2 biases (nb2 = 32)
+  ('per', 256, 18)   MAXB: sixteen full 16-row groups, all LR = 4 rounds of the
+                     update kernel's loss partials, conv1 slabs 1024; IS weights
+
+The GPU side of every shape is one gradient call and one step.  On the host,
+above 64 samples the per-sample products (forward, dX) are checked on
+layer_checks.boundary_samples(B) only, and the dW / db products, which sum
+over every sample, take K in pieces of 16 samples (tests/layer_checks.py).
+Host time of a shape's fixture and five tests together, as pytest's durations
+report it (HOST_SECONDS below): under 2 s for every shape, the whole file
+10 s, with under 1 GB resident.
 """
 
 import types
@@ -48,7 +78,14 @@ from tests import layer_checks as lc
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [('dqn', 1, 6), ('double', 5, 6), ('dqn', 32, 6), ('per', 40, 18)]
+SHAPES = [('dqn', 1, 6), ('double', 5, 6), ('dqn', 32, 6), ('per', 40, 18),
+          ('dqn', 4, 1), ('dqn', 8, 8), ('double', 6, 8), ('per', 17, 9),
+          ('double', 65, 32), ('dqn', 129, 32), ('per', 256, 18)]
+# measured host seconds per new shape: the fixture's host work and the five tests (the GPU's share is one
+# gradient call and one step, under 10 ms)
+HOST_SECONDS = {('dqn', 4, 1): 0.1, ('dqn', 8, 8): 0.3, ('double', 6, 8): 0.3, ('per', 17, 9): 0.6,
+                ('double', 65, 32): 0.7, ('dqn', 129, 32): 1.0, ('per', 256, 18): 1.8}
+DW_CHUNK = 16  # samples per piece of K in the dW products
 FWD = ('y1', 'y2', 'y3', 'h1', 'q')
 BWD = ('dz1', 'dy3', 'dy2', 'dy1')
 _FC1 = 'sequential/sequential_1/linear'
@@ -101,7 +138,7 @@ def run(request, device):
       action=action[slots].astype(np.int64), reward=reward[slots], discount=discount[slots],
       weights=np.ones(batch, np.float32) if weights is None else weights,
       grad=net.unflatten(grad.cpu().numpy()), act=after_grad, act_step=after_step,
-      td=td, loss=loss, lrn=lrn)
+      td=td, loss=loss, lrn=lrn, net=net, sel=lc.sample_subset(batch))
 
 
 def test_gradient_and_step_leave_the_same_intermediates(run):
@@ -129,15 +166,15 @@ def test_forward_kernels(run):
   rows = []
   for z in range(run.copies):
     p = run.target if z == 1 else run.online
-    act = run.act[z]
-    x = np.asarray(run.s[0 if z == 0 else 1], np.float64) / 255.0
+    act = {k: lc.take_samples(v, run.batch, run.sel) for k, v in run.act[z].items() if k in FWD}
+    x = np.asarray(run.s[0 if z == 0 else 1][run.sel], np.float64) / 255.0
     for i, name in enumerate(learner_ref.CONV_NAMES):
       w = p[name]['w']
       y = act['y%d' % (i + 1)]
       rows.append(('z%d conv%d' % (z, i + 1), lc.product_check(
           y, lc.conv_cols(x, i), w.reshape(-1, w.shape[-1]), p[name]['b'], relu=True)))
       x = y
-    flat = act['y3'].reshape(run.batch, -1)
+    flat = act['y3'].reshape(len(run.sel), -1)
     rows.append(('z%d fc1' % z, lc.product_check(act['h1'], flat, p[_FC1]['w'], p[_FC1]['b'],
                                                  relu=True)))
     rows.append(('z%d fc2' % z, lc.product_check(act['q'], act['h1'], p[_FC2]['w'],
@@ -195,9 +232,10 @@ def test_head_td_loss_dz1(run):
 
 
 def test_backward_dx_kernels(run):
-  act, p = run.act[0], run.online
+  p = run.online
+  act = {k: lc.take_samples(v, run.batch, run.sel) for k, v in run.act[0].items()}
   rows = [('fc1 dX (dy3)', lc.product_check(
-      act['dy3'], act['dz1'], p[_FC1]['w'].T, mask=act['y3'].reshape(run.batch, -1) > 0))]
+      act['dy3'], act['dz1'], p[_FC1]['w'].T, mask=act['y3'].reshape(len(run.sel), -1) > 0))]
   for layer, dy_out, dy_in, y in ((2, 'dy2', 'dy3', 'y2'), (1, 'dy1', 'dy2', 'y1')):
     a, wf, k = lc.conv_dx_operands(act[dy_in], p[learner_ref.CONV_NAMES[layer]]['w'], layer)
     rows.append(('conv%d dX (%s)' % (layer + 1, dy_out), lc.product_check(
@@ -209,13 +247,19 @@ def test_backward_dw_kernels(run):
   act, g = run.act[0], run.grad
   n = run.batch
   rows = []
-  x = np.asarray(run.s[0], np.float64) / 255.0
+  x = run.s[0]
   for i, name in enumerate(learner_ref.CONV_NAMES):
-    dy = act['dy%d' % (i + 1)]
-    dy = dy.reshape(-1, dy.shape[-1])
+    dy4 = act['dy%d' % (i + 1)]
+    dy = dy4.reshape(-1, dy4.shape[-1])
     w = g[name]['w']
-    rows.append(('conv%d dW' % (i + 1), lc.product_check(
-        w.reshape(-1, w.shape[-1]), lc.conv_cols(x, i).T, dy)))
+
+    def pieces(x=x, dy4=dy4, i=i):  # K = (sample, oh, ow), DW_CHUNK samples at a time
+      for lo in range(0, n, DW_CHUNK):
+        xc = np.asarray(x[lo:lo + DW_CHUNK], np.float64)
+        yield (lc.conv_cols(xc / 255.0 if i == 0 else xc, i).T,
+               dy4[lo:lo + DW_CHUNK].reshape(-1, dy4.shape[-1]))
+
+    rows.append(('conv%d dW' % (i + 1), lc.product_check(w.reshape(-1, w.shape[-1]), pieces(), None)))
     rows.append(('conv%d db' % (i + 1), lc.product_check(
         g[name]['b'], np.ones((1, dy.shape[0])), dy)))
     x = act['y%d' % (i + 1)]
@@ -239,3 +283,48 @@ def test_backward_dw_kernels(run):
         k_terms=n + 8, w_mag=dq_mag.sum(axis=1, keepdims=True),
         w_seq=dq32.sum(axis=1, keepdims=True))))
   lc.report(rows)
+
+
+# -- the actor at the ends of the action range, on the same learners ---------------
+
+def _observation(run):
+  return np.ascontiguousarray(run.s[1][0])
+
+
+@pytest.mark.parametrize('run', [('dqn', 4, 1)], indirect=True, ids=['dqn-4-1'])
+def test_act_with_one_action_returns_it_for_every_epsilon(run):
+  """A = 1: the greedy action and the uniform draw over one action are both
+  action 0, and max_a q is q[0]."""
+  obs = _observation(run)
+  dev = run.lrn.online.device
+  q = run.lrn.q_values(torch.from_numpy(obs[None]).to(dev))[0].cpu().numpy()
+  assert q.shape == (1,)
+  for eps in (0.0, 0.3, 1.0):
+    for c in range(40):
+      a, v = run.lrn.act(obs, eps, seed=5, counter=c)
+      assert a == 0 and v == q[0], (eps, c, a, v)
+
+
+@pytest.mark.parametrize('run', [('dqn', 129, 32)], indirect=True, ids=['dqn-129-32'])
+def test_act_ties_at_the_first_and_last_of_32_actions(run):
+  """tests/test_actor_gpu.py's tie-spreading check at A = MAXA: W2 = 0 and
+  the bias 0.25 at actions 0 and 31, 0 between, so the greedy mass is split
+  between the two ends of the action range and nothing else is drawn."""
+  tied = {m: {n: v.copy() for n, v in d.items()} for m, d in run.online.items()}
+  tied[_FC2]['w'][...] = 0.0
+  tied[_FC2]['b'][...] = 0.0
+  tied[_FC2]['b'][[0, 31]] = 0.25
+  obs = _observation(run)
+  run.lrn.set_params(tied, run.target)
+  try:
+    n = 1800
+    counts = np.zeros(32)
+    for c in range(n):
+      a, v = run.lrn.act(obs, 0.0, seed=1, counter=c)
+      counts[a] += 1
+      assert v == 0.25
+  finally:
+    run.lrn.set_params(run.online, run.target)
+  print('greedy counts at actions 0 and 31:', counts[0], counts[31])
+  assert counts[1:31].sum() == 0
+  np.testing.assert_allclose(counts[[0, 31]] / n, [0.5, 0.5], atol=4 * np.sqrt(0.25 / n))

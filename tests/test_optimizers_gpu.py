@@ -73,12 +73,18 @@ def _adam(eps=ADAM_EPS, clip=None):
 class _Handle:
   """A dqz_optimizer of its own, for the stand-alone apply."""
 
-  def __init__(self, kind, num_actions, shared, lr=LR, b1=B1, b2=B2, decay=0.95, eps=1e-8, clip=0.0):
+  def __init__(self, kind, num_actions, shared, lr=LR, b1=B1, b2=B2, decay=0.95, eps=1e-8, clip=0.0, wide=None):
+    """wide: ('c51' | 'qr', N) for a handle over a wide head's layout (dqz_c51_optimizer_create /
+    dqz_qr_optimizer_create: fc2 is [512, A N] + [A N])."""
     from dqn_mgsc_zoo_amd import _native
     self.n = _native
     cfg = _native.DqzOptimizerConfig(kind, lr, b1, b2, decay, eps, clip, num_actions, int(shared))
     self.h = ctypes.c_void_p()
-    _native.check(_native.lib().dqz_optimizer_create(ctypes.byref(cfg), ctypes.byref(self.h)))
+    if wide is None:
+      _native.check(_native.lib().dqz_optimizer_create(ctypes.byref(cfg), ctypes.byref(self.h)))
+    else:
+      create = getattr(_native.lib(), 'dqz_%s_optimizer_create' % wide[0])
+      _native.check(create(ctypes.byref(cfg), int(wide[1]), ctypes.byref(self.h)))
 
   def apply(self, th, g, m, v, count):
     n = self.n
@@ -96,9 +102,12 @@ class _Handle:
       self.h = ctypes.c_void_p()
 
 
-def _real_mask(num_actions, shared):
+def _real_mask(num_actions, shared, wide=None):
   from dqn_mgsc_zoo_amd import _native
-  offs, sizes, total = _native.param_layout(num_actions, shared)
+  if wide is None:
+    offs, sizes, total = _native.param_layout(num_actions, shared)
+  else:
+    offs, sizes, total = getattr(_native, wide[0] + '_param_layout')(num_actions, wide[1])
   real = np.zeros(total, bool)
   for o, s in zip(offs, sizes):
     real[o:o + s] = True
@@ -157,19 +166,35 @@ def _bits(t):
   return t.detach().cpu().numpy().view(np.int32)
 
 
+# The ends of the layout: 1 and 32 actions (dqz_optimizer_create's limits; with a shared bias the last leaf
+# is one float whatever A is), and through the wide heads' creates A N = 2 (the smallest fc2 either takes),
+# 1024 (the categorical head's limit) and 4096 (the quantile head's).
+WIDE_LAYOUTS = [('c51', 1, 2), ('qr', 2, 1), ('c51', 16, 64), ('qr', 16, 256)]
+
+
+@pytest.mark.parametrize('wide', WIDE_LAYOUTS, ids=lambda w: '%s-%dx%d' % w)
+@pytest.mark.parametrize('kind,eps', [('adam', ADAM_EPS), ('rmsprop', 1e-8)])
+def test_apply_from_injected_gradients_on_wide_layouts(device, kind, eps, wide):
+  """test_apply_from_injected_gradients on the layouts of dqz_c51_param_layout /
+  dqz_qr_param_layout, against tests/optim_ref.py at the same bars."""
+  head, a, n = wide
+  test_apply_from_injected_gradients(device, kind, eps, a, False, wide=(head, n))
+
+
 @pytest.mark.parametrize('shared', [False, True])
-@pytest.mark.parametrize('num_actions', [3, 6, 18])
+@pytest.mark.parametrize('num_actions', [1, 3, 6, 18, 32])
 @pytest.mark.parametrize('kind,eps', [('adam', 1e-8), ('adam', ADAM_EPS), ('rmsprop', 1e-8)])
-def test_apply_from_injected_gradients(device, kind, eps, num_actions, shared):
+def test_apply_from_injected_gradients(device, kind, eps, num_actions, shared, wide=None):
   from dqn_mgsc_zoo_amd import _native
-  real = _real_mask(num_actions, shared)
-  rng = np.random.default_rng(100 + num_actions + int(shared))
+  real = _real_mask(num_actions, shared, wide)
+  assert real.size % 64 == 0 and not real.all()  # every layout here has padding for the apply to skip
+  rng = np.random.default_rng(100 + num_actions + int(shared) + (0 if wide is None else wide[1]))
   th0, m0, v0 = _start_state(rng, real)
   th, m, v = (torch.from_numpy(a).to(device) for a in (th0, m0, v0))
   count = torch.zeros((1,), dtype=torch.int32, device=device)
   is_adam = kind == 'adam'
   lr, b1, b2, decay, e = _f32(LR), _f32(B1), _f32(B2), _f32(0.95), _f32(eps)
-  h = _Handle(_native.OPT_ADAM if is_adam else _native.OPT_RMSPROP, num_actions, shared, eps=eps)
+  h = _Handle(_native.OPT_ADAM if is_adam else _native.OPT_RMSPROP, num_actions, shared, eps=eps, wide=wide)
   try:
     for step in range(3):
       g_np = _injected_grad(rng, real)
@@ -252,6 +277,59 @@ def test_global_norm_and_clip(device, seed, want):
     _check_moment(got[2][real], v_ref[real], prev[2][real], g_c[real], b2, 2, 'clipped v')
   finally:
     for h in (plain, loose, tight):
+      h.close()
+
+
+def test_global_norm_and_clip_on_a_wide_layout(device):
+  """test_global_norm_and_clip's checks on the quantile head's widest layout
+  (A N = 4096: an fc2 of 2 M weights, whose bias leaf fills its 64-float
+  blocks exactly), from an injected gradient: the norm is the float64 norm
+  of the real elements whatever the padding holds, an inactive clip changes
+  no bit, an active one is the reference's clipped gradient through Adam."""
+  from dqn_mgsc_zoo_amd import _native
+  a, wide = 16, ('qr', 256)
+  real = _real_mask(a, False, wide)
+  rng = np.random.default_rng(7)
+  th0, m0, v0 = _start_state(rng, real)
+  g_np = (rng.standard_normal(real.size) * 10.0 ** rng.uniform(-6, -2, real.size)).astype(np.float32)
+  g_np[~real] = 0.0
+  norm64 = float(np.sqrt(np.sum(g_np[real].astype(np.float64) ** 2)))
+  tight_clip = 0.5 * norm64
+  assert norm64 < 10.0
+  g_dirty = g_np.copy()
+  g_dirty[~real] = 3.0  # garbage in the caller's padding does not reach the norm
+  kw = dict(eps=ADAM_EPS, wide=wide)
+  handles = dict(plain=_Handle(_native.OPT_ADAM, a, False, **kw), loose=_Handle(_native.OPT_ADAM, a, False, clip=10.0, **kw),
+                 tight=_Handle(_native.OPT_ADAM, a, False, clip=tight_clip, **kw))
+  try:
+    outs = {}
+    for name, h in handles.items():
+      for g_host in (g_np, g_dirty):
+        th, m, v = (torch.from_numpy(x).to(device) for x in (th0, m0, v0))
+        count = torch.zeros((1,), dtype=torch.int32, device=device)
+        h.apply(th, torch.from_numpy(g_host).to(device), m, v, count)
+        run = (_bits(th), _bits(m), _bits(v), _bits(h.norm()), int(count.item()))
+        if name in outs:  # dirty padding: the same bits
+          for x, y in zip(outs[name], run):
+            assert np.array_equal(x, y), name
+        outs[name] = run
+      gn = float(outs[name][3].view(np.float32)[0])
+      assert abs(gn - norm64) <= 2.0**-22 * norm64, (name, gn, norm64)
+      for arr in outs[name][:3]:  # the padding of theta, m and v stays bit-zero
+        assert not arr[~real].any()
+    for k in range(3):
+      assert np.array_equal(outs['plain'][k], outs['loose'][k])
+    assert not np.array_equal(outs['tight'][0], outs['plain'][0])
+    lr, b1, b2, e = _f32(LR), _f32(B1), _f32(B2), _f32(ADAM_EPS)
+    g_c, n_ref = optim_ref.clip_by_global_norm(g_np, _f32(tight_clip))
+    assert abs(n_ref - norm64) < 1e-12
+    t_ref, m_ref, v_ref, _ = optim_ref.adam(th0, g_c, m0, v0, 0, lr, b1, b2, e)
+    got = [x.view(np.float32) for x in outs['tight'][:3]]
+    _check_theta(got[0][real], t_ref[real], th0[real], 'wide clipped')
+    _check_moment(got[1][real], m_ref[real], m0[real], g_c[real], b1, 1, 'wide clipped m')
+    _check_moment(got[2][real], v_ref[real], v0[real], g_c[real], b2, 2, 'wide clipped v')
+  finally:
+    for h in handles.values():
       h.close()
 
 

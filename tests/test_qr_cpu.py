@@ -246,6 +246,9 @@ def _refusals():
       ('create-too-many-quantiles', create(_cfg(), 257), 'num_quantiles must be in [1, 256]'),
       ('create-too-wide', create(_cfg(num_actions=17), 241), 'num_actions * num_quantiles must be <= 4096'),
       ('create-batch-one', create(_cfg(batch=1), 201), 'batch must be in [2, 256]'),
+      # the first value past each limit (N = 257, A N = 4097 and batch 1 are above)
+      ('create-33-actions', create(_cfg(num_actions=33), 124), 'num_actions must be in [1, 32]'),
+      ('create-batch-257', create(_cfg(batch=257), 201), 'batch must be in [2, 256]'),
       ('create-double-q', create(_cfg(algo=1), 201), 'the quantile head runs on a DQN learner'),
       ('create-huber-zero', create(_cfg(), 201, P, 0.0), huber),
       ('create-huber-negative', create(_cfg(), 201, P, -1.0), huber),
@@ -382,3 +385,34 @@ def test_network_spec_surface(lib):
       networks.qr_atari_network(6, bad)
   with pytest.raises(ValueError, match='num_quantiles < 1'):
     networks.qr_atari_network(6, [])
+
+
+
+# -- the input conditions of the GPU tests' corner shapes, without a GPU ---------
+
+def _corner_ids():
+  from tests import test_qr_gpu as gpu  # pylint: disable=g-import-not-at-top
+  return gpu.CORNERS
+
+
+@pytest.mark.parametrize('shape', _corner_ids(), ids=lambda s: '%dx%dx%d-kappa%g' % s)
+def test_corner_shapes_meet_their_input_conditions(lib, shape):
+  """tests/test_qr_gpu.py's _check_conditions on each corner shape's pinned
+  seed, in float64 on the CPU: every condition but the ones WAIVED names for
+  that shape, and each waiver is one the shape makes impossible (or, for the
+  kink-free draw, one its tests do not need)."""
+  from tests import test_qr_gpu as gpu  # pylint: disable=g-import-not-at-top
+  b, a, n, kappa = shape
+  case = gpu._case(*shape)  # pylint: disable=protected-access
+  gpu._check_conditions(case)  # pylint: disable=protected-access
+  waived = gpu.WAIVED.get(shape, set())
+  for what in ('absent action', 'best action not 0', 'margin'):
+    assert (what in waived) == (a == 1), what
+  assert ('both signs' in waived) == (n == 1)
+  assert ('kink-free draw' in waived) == (shape in gpu.STAGE_ONLY)
+  assert waived <= {'absent action', 'best action not 0', 'margin', 'both signs', 'kink-free draw'}
+  assert len(case['slots']) == b and case['slots'][0] == gpu.SPECIAL and kappa == gpu.KAPPA
+  if shape not in gpu.STAGE_ONLY:  # the end-to-end step's batch is kink-free
+    s = helpers.stacks_from(case['host']['frames'], case['host']['fidx'], case['slots'], 0)
+    assert learner_ref.relu_margin(case['online'], s) >= 1e-6
+  assert a * n <= 4096 and 1 <= n <= 256 and 1 <= a <= 32 and 2 <= b <= 256

@@ -1,5 +1,5 @@
-"""CPU: the learner-step entries and dqz_per_sample refuse bad arguments
-before any device call and before any handle is dereferenced.
+"""CPU: the learner-step entries, dqz_learner_create and dqz_per_sample refuse
+bad arguments before any device call and before any handle is dereferenced.
 
 One table: each row is a call, the status it returns and a fragment of
 dqz_last_error().  The handles are fake non-null addresses, so a row passes
@@ -121,6 +121,16 @@ def _rows():
       ('usp-negative', dict(usp=-0.1), 'Require 0 <= uniform_sample_probability <= 1.'),
   ]
   rows += [('per-sample-' + name, 'dqz_per_sample', _per_sample(**kw), frag) for name, kw, frag in sample]
+  # dqz_learner_create(config, out): the first value past each limit (batch 1 .. 256, 1 .. 32 actions), refused
+  # before the first HIP call
+  from dqn_mgsc_zoo_amd import _native  # pylint: disable=g-import-not-at-top
+  handle = ctypes.c_void_p()
+  create = lambda batch, a: (ctypes.byref(_native.DqzLearnerConfig(batch, a, 0, 2.5e-4, 0.95, 1e-5, 1.0 / 32)),
+                             ctypes.byref(handle))
+  rows += [('create-batch-zero', 'dqz_learner_create', create(0, 6), 'batch must be in [1, 256]'),
+           ('create-batch-257', 'dqz_learner_create', create(257, 6), 'batch must be in [1, 256]'),
+           ('create-no-actions', 'dqz_learner_create', create(256, 0), 'num_actions must be in [1, 32]'),
+           ('create-33-actions', 'dqz_learner_create', create(1, 33), 'num_actions must be in [1, 32]')]
   return rows
 
 
