@@ -116,6 +116,11 @@ class DqzOptimizerConfig(ctypes.Structure):
   ]
 
 
+class DqzWideOptions(ctypes.Structure):
+  """dqz_wide_options: double-Q selection and importance weights on a wide head."""
+  _fields_ = [('double_q', ctypes.c_int), ('weighted', ctypes.c_int)]
+
+
 class DqzAction(ctypes.Structure):
   _fields_ = [('action', ctypes.c_int32), ('value', ctypes.c_float)]
 
@@ -358,11 +363,33 @@ _WIDE_SIGNATURES = {
         _int, [_vp, _vp, _vp, _int, ctypes.c_double, ctypes.c_uint64,
                ctypes.c_uint64, _vp, _vp]),
     'debug_check': (_int, [_int, ctypes.c_uint]),
+    # a head created with dqz_wide_options
+    'step_w': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
+         _vp, _vp, _vp]),
+    'grad_w': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
+         _vp, _vp]),
+    'profile_w': (
+        _int,
+        [_vp, ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore), _vp, _vp,
+         _vp, _int, ctypes.POINTER(ctypes.c_float), _vp]),
+    'outputs_opt': (_int, [_vp, _vp, _vp, _vp]),
+    'debug_check_opt': (
+        _int, [_int, ctypes.c_uint, ctypes.POINTER(DqzWideOptions)]),
 }
 for _prefix in ('dqz_c51_', 'dqz_qr_'):
   SIGNATURES.update({_prefix + k: v for k, v in _WIDE_SIGNATURES.items()})
 SIGNATURES['dqz_c51_create'] = (
     _int, [ctypes.POINTER(DqzLearnerConfig), _int, _vp, ctypes.POINTER(_vp)])
+SIGNATURES['dqz_c51_create_opt'] = (
+    _int, [ctypes.POINTER(DqzLearnerConfig), _int, _vp,
+           ctypes.POINTER(DqzWideOptions), ctypes.POINTER(_vp)])
+SIGNATURES['dqz_qr_create_opt'] = (
+    _int, [ctypes.POINTER(DqzLearnerConfig), _int, _vp, ctypes.c_float,
+           ctypes.POINTER(DqzWideOptions), ctypes.POINTER(_vp)])
 SIGNATURES['dqz_qr_create'] = (
     _int, [ctypes.POINTER(DqzLearnerConfig), _int, _vp, ctypes.c_float,
            ctypes.POINTER(_vp)])

@@ -18,7 +18,11 @@
 //                      P[a*] onto the support, the cross-entropy, dlogits of
 //                      the taken action and the dz1 row (four lanes per W2
 //                      row).  Forward / actor mode stops after q_values (and
-//                      the eps-greedy draw).
+//                      the eps-greedy draw).  WIDE_DOUBLE: a* comes from a third
+//                      copy, online(s_t) (rlax.categorical_double_q_learning);
+//                      WIDE_WEIGHTED: the cotangent carries the sample's
+//                      importance weight and clip(|loss_b|, 0, 100) is the
+//                      sample's new priority (rainbow/agent.py:85-150,198).
 //   c51_fc2_grad_kernel  dW2 / db2 from h1 and dlogits, every element written
 //                      (zeros for actions absent from the batch), summed in
 //                      sample order by one thread per element.
@@ -129,6 +133,12 @@ DQZ_OTHER_KERNEL __launch_bounds__(256) void c51_logits_kernel(C51LogitsArgs a) 
   }
 }
 
+// What a wide head's step does beyond rlax's plain rule (a head kernel's template argument, bits): the plain
+// instantiation is the kernel as it was.
+constexpr int WIDE_DOUBLE = 1;    // a* = argmax_a q_values of copy 2, online(s_t), instead of the target's own
+constexpr int WIDE_WEIGHTED = 2;  // loss = mean_b(w_b loss_b): the cotangent times w_b; the priority clip(|loss_b|, 0, 100)
+constexpr float WIDE_MAX_PRIORITY = 100.f;  // rainbow/agent.py:198
+
 struct C51HeadArgs {
   const float* logits;   // [Z][B][A N]
   const float* h1;       // [Z][B][512]; copy 0's ReLU decisions gate dz1
@@ -139,8 +149,8 @@ struct C51HeadArgs {
   float* qv;          // [Z][B][A] q_values
   float* la;          // [B][N] online logits of the taken action
   float* dl;          // [B][N] d loss / d those logits
-  int32_t* astar;     // [B] argmax_a q_target
-  float* loss_part;   // [B]
+  int32_t* astar;     // [B] argmax_a q_target (WIDE_DOUBLE: of copy 2's q_values)
+  float* loss_part;   // [B] what the update sums to the step's loss: loss_b (WIDE_WEIGHTED: w_b loss_b)
   float* gq;          // [B] <- 0 (the scalar head's cotangent: unused downstream, never stale)
   int32_t* ga;        // [B] <- a_b
   float* dz1;         // [B][512]
@@ -148,6 +158,10 @@ struct C51HeadArgs {
   dqz_action* act_out;
   double eps;
   uint64_t act_seed, act_ctr;
+  // WIDE_WEIGHTED alone (last, so that the plain kernels read their arguments where they always did)
+  const float* weights;  // [B] importance weights
+  float* loss_b;         // [B] the unweighted per-sample loss
+  float* prio;           // [B] clip(|loss_b|, 0, 100): the learner's td buffer, which dqz_per_write_back reads
 };
 
 // Maximum of a wave's floats in every lane (exact in any order).
@@ -163,17 +177,25 @@ __device__ __forceinline__ float wave_max(float m) {
 // equal bits.  The record is read by every thread through the same (uniform)
 // address, and the W2 operands of dz1 (the taken action's N columns of every
 // row) are requested as soon as the action is known, under everything else
-// the workgroup does.
+// the workgroup does.  With WIDE_DOUBLE copy 2's logits never enter LDS: the
+// wave that owns a row of it reads the row from global memory and leaves the
+// action's q_value alone.  MODE = 0 compiles to the instructions the kernel had
+// before it took a mode (a shared __device__ body behind thin kernels does not:
+// the register allocation moves).
+template <int MODE>
 DQZ_OTHER_KERNEL __launch_bounds__(512) void c51_head_kernel(C51HeadArgs h) {
+  constexpr bool DQ = MODE & WIDE_DOUBLE, WT = MODE & WIDE_WEIGHTED;
   __shared__ float s_lg[2][C51_MAXOUT];
   __shared__ float s_z[C51_MAXN], s_p[C51_MAXN];
   __shared__ float s_dlp[3 + 16 * ((C51_MAXN + 3 + 15) / 16) + 1];  // dlogits at [3, 3 + N), zeros around them
   __shared__ float s_part[8][C51_MAXN];
   __shared__ float s_q[2][MAXA], s_mx[2][MAXA], s_se[2][MAXA];
+  __shared__ float s_qs[DQ ? MAXA : 1];  // the selector's q_values (copy 2)
   const int b = blockIdx.x, n = threadIdx.x, lane = n & 63, wave = n >> 6;
   const int A = h.A, N = h.N, AN = A * N, B = h.B, Z = h.Z;
+  const int ZL = DQ ? 2 : Z;  // copies held in LDS
   int a_tm1 = 0;
-  float r = 0.f, d = 0.f;
+  float r = 0.f, d = 0.f, wt = 1.f;
   // dz1's operands: four lanes share a row of W2 (rows 128 p + n / 4, p = 0 .. 3), each loading the aligned
   // float4s sub + 4 j of the 16-byte window that holds the row's N weights of the taken action, which starts
   // `off` floats into it.  A thread per row would touch 64 cache lines per load instruction (rows are A N
@@ -189,6 +211,7 @@ DQZ_OTHER_KERNEL __launch_bounds__(512) void c51_head_kernel(C51HeadArgs h) {
     a_tm1 = min(max(__float_as_int(rv.x), 0), A - 1);  // a record outside [0, A) reads inside the buffers
     r = rv.y;
     d = rv.z;
+    if (WT) wt = h.weights[b];
 #pragma unroll
     for (int p = 0; p < DZ_P; ++p) {
       const int row = 128 * p + (n >> 2);
@@ -200,7 +223,7 @@ DQZ_OTHER_KERNEL __launch_bounds__(512) void c51_head_kernel(C51HeadArgs h) {
       hv[p] = h.h1[(int64_t)b * HID + row];
     }
   }
-  for (int e = n; e < Z * AN; e += HID) {
+  for (int e = n; e < ZL * AN; e += HID) {
     const int z = e / AN, c = e % AN;
     s_lg[z][c] = h.logits[((int64_t)z * B + b) * AN + c];
   }
@@ -210,15 +233,24 @@ DQZ_OTHER_KERNEL __launch_bounds__(512) void c51_head_kernel(C51HeadArgs h) {
   // softmax statistics and q_values[z][a] = sum_j softmax_j z_j
   for (int row = wave; row < Z * A; row += 8) {
     const int z = row / A, a = row % A;
-    const float x = lane < N ? s_lg[z][a * N + lane] : -INFINITY;
+    float x = -INFINITY;
+    if (DQ && z == 2) {  // wave-uniform
+      if (lane < N) x = h.logits[((int64_t)2 * B + b) * AN + a * N + lane];
+    } else if (lane < N) {
+      x = s_lg[z][a * N + lane];
+    }
     const float mx = wave_max(x);
     const float e = lane < N ? expf(x - mx) : 0.f;
     const float se = wave_sum(e);
     const float qa = wave_sum(lane < N ? (e / se) * s_z[lane] : 0.f);
     if (lane == 0) {
-      s_mx[z][a] = mx;
-      s_se[z][a] = se;
-      s_q[z][a] = qa;
+      if (DQ && z == 2) {
+        s_qs[a] = qa;
+      } else {
+        s_mx[z][a] = mx;
+        s_se[z][a] = se;
+        s_q[z][a] = qa;
+      }
       h.qv[((int64_t)z * B + b) * A + a] = qa;
     }
   }
@@ -234,10 +266,11 @@ DQZ_OTHER_KERNEL __launch_bounds__(512) void c51_head_kernel(C51HeadArgs h) {
   }
   int am = 0;  // jnp.argmax: first maximum; every thread forms it from the same LDS values
   {
-    float best = s_q[1][0];
+    const float* sel = DQ ? s_qs : s_q[1];
+    float best = sel[0];
     for (int a = 1; a < A; ++a)
-      if (s_q[1][a] > best) {
-        best = s_q[1][a];
+      if (sel[a] > best) {
+        best = sel[a];
         am = a;
       }
   }
@@ -267,7 +300,8 @@ DQZ_OTHER_KERNEL __launch_bounds__(512) void c51_head_kernel(C51HeadArgs h) {
 #pragma unroll
     for (int w = 0; w < 8; ++w) m += s_part[w][lane];
     const float l = s_lg[0][a_tm1 * N + k], xs = l - s_mx[0][a_tm1], se = s_se[0][a_tm1];
-    const float g = (expf(xs) / se - m) / (float)B;
+    float g = (expf(xs) / se - m) / (float)B;
+    if (WT) g = wt == 0.f ? 0.f : g * wt;  // a weight of 0: +0.0, whatever g's sign
     const float ce = wave_sum(lane < N ? m * (xs - logf(se)) : 0.f);
     if (lane < N) {
       s_dlp[3 + lane] = g;
@@ -275,7 +309,13 @@ DQZ_OTHER_KERNEL __launch_bounds__(512) void c51_head_kernel(C51HeadArgs h) {
       h.dl[(int64_t)b * N + lane] = g;
     }
     if (lane == 0) {
-      h.loss_part[b] = -ce;
+      if (WT) {
+        h.loss_part[b] = wt * -ce;
+        h.loss_b[b] = -ce;
+        h.prio[b] = fminf(fabsf(ce), WIDE_MAX_PRIORITY);
+      } else {
+        h.loss_part[b] = -ce;
+      }
       h.gq[b] = 0.f;
       h.ga[b] = a_tm1;
       h.astar[b] = am;

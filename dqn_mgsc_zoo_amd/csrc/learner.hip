@@ -944,12 +944,14 @@ int dqz::wide_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, cons
   const WideHead& c = *r.wide;
   const bool qr = c.kind == WIDE_QR;
   const int B = L->cfg.batch, A = L->cfg.num_actions, N = c.N;
+  const int Z = L->Z;  // 3 with double_q: the selector, online(s_t), is copy 2
+  const int mode = (c.double_q ? WIDE_DOUBLE : 0) | (c.weighted ? WIDE_WEIGHTED : 0);
   if (which == WIDE_OUTPUTS) {
     const NetZ nz{{P->online, P->target, P->online}, {0, 1, 1}};
-    return c51_logits(L, nz, 2, B, A * N, c.out, st);
+    return c51_logits(L, nz, Z, B, A * N, c.out, st);
   }
   if (which == WIDE_HEAD && qr) {
-    QrHeadArgs h = qr_head_args(c, 2, B, A);
+    QrHeadArgs h = qr_head_args(c, Z, B, A);
     h.rec = reinterpret_cast<const float4*>(L->rec);
     h.qv = c.qv;
     h.theta = c.taken;
@@ -959,9 +961,14 @@ int dqz::wide_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, cons
     h.loss_part = L->loss_part;
     h.gq = L->gq;
     h.ga = L->ga;
-    hipLaunchKernelGGL(qr_head_kernel, dim3(B), dim3(QR_THREADS), 0, st, h);
+    h.weights = r.is_weights;
+    h.loss_b = c.loss_b;
+    h.prio = L->td;
+    auto* const k = mode == 3 ? qr_head_kernel<3> : mode == 2 ? qr_head_kernel<2>
+                  : mode == 1 ? qr_head_kernel<1> : qr_head_kernel<0>;
+    hipLaunchKernelGGL(k, dim3(B), dim3(QR_THREADS), 0, st, h);
   } else if (which == WIDE_HEAD) {
-    C51HeadArgs h = c51_head_args(c, 2, B, A);
+    C51HeadArgs h = c51_head_args(c, Z, B, A);
     h.h1 = L->h1;
     h.w2 = P->online + L->off[8];
     h.rec = reinterpret_cast<const float4*>(L->rec);
@@ -973,7 +980,12 @@ int dqz::wide_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, cons
     h.gq = L->gq;
     h.ga = L->ga;
     h.dz1 = L->dz1;
-    hipLaunchKernelGGL(c51_head_kernel, dim3(B), dim3(HID), 0, st, h);
+    h.weights = r.is_weights;
+    h.loss_b = c.loss_b;
+    h.prio = L->td;
+    auto* const k = mode == 3 ? c51_head_kernel<3> : mode == 2 ? c51_head_kernel<2>
+                  : mode == 1 ? c51_head_kernel<1> : c51_head_kernel<0>;
+    hipLaunchKernelGGL(k, dim3(B), dim3(HID), 0, st, h);
   } else if (which == WIDE_DZ1) {  // the quantile head alone (WideHead::dout)
     QrDz1Args d{};
     d.dout = c.dout;
@@ -1035,11 +1047,11 @@ static int wide_forward_q(dqz_wide* W, const float* params, const Conv1Src& src,
   if (W->head.kind == WIDE_QR) {
     QrHeadArgs h = qr_head_args(W->head, 1, n, W->A);
     set_forward(&h, q_out, act);
-    hipLaunchKernelGGL(qr_head_kernel, dim3(n), dim3(QR_THREADS), 0, st, h);
+    hipLaunchKernelGGL(qr_head_kernel<0>, dim3(n), dim3(QR_THREADS), 0, st, h);
   } else {
     C51HeadArgs h = c51_head_args(W->head, 1, n, W->A);
     set_forward(&h, q_out, act);
-    hipLaunchKernelGGL(c51_head_kernel, dim3(n), dim3(HID), 0, st, h);
+    hipLaunchKernelGGL(c51_head_kernel<0>, dim3(n), dim3(HID), 0, st, h);
   }
   DQZ_HIP(hipGetLastError());
   return DQZ_OK;
@@ -1079,23 +1091,30 @@ static int wide_destroy(dqz_wide* W) {
 }
 
 // The back half of both creates, behind wide_check_config and the entry's own checks of its grid (host, [N])
+// opt: null for the plain creates.  With double_q the inner learner is the three-copy one (DQZ_ALGO_DOUBLE's Z),
+// on the wide layout like the plain one: no shared bias.
 static int wide_create(WideKind kind, const dqz_learner_config* cfg, int N, const float* grid_host, float kappa,
-                       dqz_wide** out) {
+                       const dqz_wide_options* opt, dqz_wide** out) {
   const WideDesc& d = kWide[kind];
+  const int double_q = opt ? opt->double_q : 0, weighted = opt ? opt->weighted : 0;
+  dqz_learner_config inner = *cfg;
+  if (double_q) inner.algo = DQZ_ALGO_DOUBLE;
   dqz_learner* L = nullptr;
-  if (int rc = dqz_learner_create(cfg, &L)) return rc;
+  if (int rc = dqz_learner_create(&inner, &L)) return rc;
   const int A = cfg->num_actions;
   wide_param_layout(A, N, L->off, L->sz, &L->total);  // leaves 0-7 unchanged; the scalar head's L->q stays unused
+  L->shared_bias = 0;
   dqz_wide* W = new dqz_wide();
   W->L = L;
   W->A = A;
   W->N = N;
   // every piece on a 64-float boundary, in WideHead's order; astar [B] last
   const auto pad = [](int64_t n) { return (n + 63) / 64 * 64; };
-  const int64_t B = cfg->batch, AN = (int64_t)A * N;
-  const int64_t n_grid = pad(N), n_out = pad(2 * B * AN), n_tk = pad(B * N);
-  const int64_t n_do = kind == WIDE_QR ? pad(B * AN + QR_PAD) : 0, n_qv = pad(2 * B * A);
-  const int64_t floats = n_grid + n_out + 2 * n_tk + n_do + n_qv + B;
+  const int64_t B = cfg->batch, AN = (int64_t)A * N, Z = L->Z;
+  const int64_t n_grid = pad(N), n_out = pad(Z * B * AN), n_tk = pad(B * N);
+  const int64_t n_do = kind == WIDE_QR ? pad(B * AN + QR_PAD) : 0, n_qv = pad(Z * B * A);
+  const int64_t n_as = pad(B), n_lb = weighted ? pad(B) : 0;  // loss_b behind astar, in a weighted head alone
+  const int64_t floats = n_grid + n_out + 2 * n_tk + n_do + n_qv + n_as + n_lb;
   if (hipMalloc(&W->block, floats * sizeof(float)) != hipSuccess ||
       hipMemset(W->block, 0, floats * sizeof(float)) != hipSuccess) {
     if (W->block) (void)hipFree(W->block);
@@ -1115,6 +1134,9 @@ static int wide_create(WideKind kind, const dqz_learner_config* cfg, int N, cons
   h.dout = n_do ? h.dtaken + n_tk : nullptr;
   h.qv = h.dtaken + n_tk + n_do;
   h.astar = reinterpret_cast<int32_t*>(h.qv + n_qv);
+  h.double_q = double_q;
+  h.weighted = weighted;
+  h.loss_b = n_lb ? h.qv + n_qv + n_as : nullptr;
   if (hipMemcpy(p, grid_host, sizeof(float) * N, hipMemcpyHostToDevice) != hipSuccess) {
     (void)wide_destroy(W);
     return fail(DQZ_ERR_HIP, "copy of the %s failed", d.grid);
@@ -1129,24 +1151,32 @@ static int wide_learner(dqz_wide* W, dqz_learner** out) {
   return DQZ_OK;
 }
 
-static int wide_step(dqz_wide* W, const dqz_params* P, const dqz_store* S, const int32_t* slots, dqz_optimizer* o,
-                     int32_t* count, void* stream) {
+// is_weights: null from the plain entries; the _w entries have refused a null one
+static int wide_step(dqz_wide* W, const dqz_params* P, const dqz_store* S, const int32_t* slots,
+                     const float* is_weights, dqz_optimizer* o, int32_t* count, void* stream) {
   if (!W) return fail(DQZ_ERR_INVALID, "null argument");
-  return step_then_apply(W->L, P, S, {.slots = slots, .wide = &W->head}, o, count, stream);
+  return step_then_apply(W->L, P, S, {.slots = slots, .is_weights = is_weights, .wide = &W->head}, o, count, stream);
 }
 
-static int wide_grad(dqz_wide* W, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
-                     void* stream) {
+static int wide_grad(dqz_wide* W, const dqz_params* P, const dqz_store* S, const int32_t* slots,
+                     const float* is_weights, float* grad_out, void* stream) {
   if (!W) return fail(DQZ_ERR_INVALID, "null argument");
   if (!grad_out) return fail(DQZ_ERR_INVALID, "null grad_out");
-  return step_impl(W->L, P, S, {.slots = slots, .gout = grad_out, .wide = &W->head}, stream);
+  return step_impl(W->L, P, S, {.slots = slots, .is_weights = is_weights, .gout = grad_out, .wide = &W->head},
+                   stream);
 }
 
-static int wide_profile(dqz_wide* W, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
-                        int iters, float* phase_ms, void* stream) {
+static int wide_profile(dqz_wide* W, const dqz_params* P, const dqz_store* S, const int32_t* slots,
+                        const float* is_weights, float* grad_out, int iters, float* phase_ms, void* stream) {
   if (!W) return fail(DQZ_ERR_INVALID, "null argument");
   if (!grad_out) return fail(DQZ_ERR_INVALID, "null grad_out");
-  return profile_step(W->L, P, S, {.slots = slots, .gout = grad_out, .wide = &W->head}, iters, phase_ms, stream);
+  return profile_step(W->L, P, S, {.slots = slots, .is_weights = is_weights, .gout = grad_out, .wide = &W->head},
+                      iters, phase_ms, stream);
+}
+
+static int wide_check_weights(const void* handle, const float* is_weights) {
+  if (!handle || !is_weights) return fail(DQZ_ERR_INVALID, "null argument");
+  return DQZ_OK;
 }
 
 static int wide_outputs(dqz_wide* W, float* taken, float* q_values, float* loss_b, float* loss, int32_t* a_star,
@@ -1158,10 +1188,27 @@ static int wide_outputs(dqz_wide* W, float* taken, float* q_values, float* loss_
     void* dst;
     const void* src;
     int64_t n;
-  } rows[] = {{taken, W->head.taken, B * W->N},  {q_values, W->head.qv, 2 * B * W->A}, {loss_b, W->L->loss_part, B},
-              {loss, W->L->loss, 1},             {a_star, W->head.astar, B}};
+  } rows[] = {{taken, W->head.taken, B * W->N},
+              {q_values, W->head.qv, 2 * B * W->A},
+              // a weighted head's loss_part holds w_b loss_b; loss_b is in a buffer of its own
+              {loss_b, W->head.loss_b ? W->head.loss_b : W->L->loss_part, B},
+              {loss, W->L->loss, 1},
+              {a_star, W->head.astar, B}};
   for (const auto& r : rows)
     if (r.dst) DQZ_HIP(hipMemcpyAsync(r.dst, r.src, 4 * r.n, hipMemcpyDeviceToDevice, st));
+  return DQZ_OK;
+}
+
+// What a head with options adds to wide_outputs: the selector's q_values and the priorities
+static int wide_outputs_opt(dqz_wide* W, float* q_selector, float* priorities, void* stream) {
+  if (!W) return fail(DQZ_ERR_INVALID, "null argument");
+  if (q_selector && !W->head.double_q) return fail(DQZ_ERR_INVALID, "q_selector needs a head created with double_q");
+  if (priorities && !W->head.weighted) return fail(DQZ_ERR_INVALID, "priorities need a head created with weighted");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t B = W->L->cfg.batch;
+  if (q_selector)
+    DQZ_HIP(hipMemcpyAsync(q_selector, W->head.qv + 2 * B * W->A, 4 * B * W->A, hipMemcpyDeviceToDevice, st));
+  if (priorities) DQZ_HIP(hipMemcpyAsync(priorities, W->L->td, 4 * B, hipMemcpyDeviceToDevice, st));
   return DQZ_OK;
 }
 
@@ -1169,7 +1216,7 @@ static int wide_debug(dqz_wide* W, float* outputs, float* dtaken, void* stream) 
   if (!W) return fail(DQZ_ERR_INVALID, "null argument");
   hipStream_t st = (hipStream_t)stream;
   const int64_t B = W->L->cfg.batch;
-  if (outputs) DQZ_HIP(hipMemcpyAsync(outputs, W->head.out, 4 * 2 * B * W->A * W->N, hipMemcpyDeviceToDevice, st));
+  if (outputs) DQZ_HIP(hipMemcpyAsync(outputs, W->head.out, 4 * W->L->Z * B * W->A * W->N, hipMemcpyDeviceToDevice, st));
   if (dtaken) DQZ_HIP(hipMemcpyAsync(dtaken, W->head.dtaken, 4 * B * W->N, hipMemcpyDeviceToDevice, st));
   return DQZ_OK;
 }
@@ -1196,13 +1243,21 @@ static int wide_act(dqz_wide* W, const float* params, const uint8_t* states, int
   return wide_forward_q(W, params, src, 0, n, W->head.qv, &act, (hipStream_t)stream);
 }
 
-static int wide_debug_check(WideKind kind, int batch, unsigned request) {
+static int wide_check_options(const dqz_wide_options* opt) {
+  if (!opt) return fail(DQZ_ERR_INVALID, "null argument");
+  if ((opt->double_q != 0 && opt->double_q != 1) || (opt->weighted != 0 && opt->weighted != 1))
+    return fail(DQZ_ERR_INVALID, "double_q and weighted must be 0 or 1");
+  return DQZ_OK;
+}
+
+// opt: null for the plain probes (a default WideHead, which keeps refusing weights)
+static int wide_debug_check(WideKind kind, int batch, unsigned request, const dqz_wide_options* opt) {
   // a host-only learner, parameters and store whose pointers are set but never followed: check_step alone runs
   static float word[4];
   dqz_learner L{};
   L.cfg.batch = batch;
   L.cfg.num_actions = 6;
-  L.cfg.algo = DQZ_ALGO_DQN;
+  L.cfg.algo = opt && opt->double_q ? DQZ_ALGO_DOUBLE : DQZ_ALGO_DQN;
   const dqz_params P{word, word, word, word};
   dqz_store S{};
   S.frames = reinterpret_cast<uint8_t*>(word);
@@ -1224,6 +1279,10 @@ static int wide_debug_check(WideKind kind, int batch, unsigned request) {
   const PerWbArgs wb{};
   WideHead head{};
   head.kind = kind;
+  if (opt) {
+    head.double_q = opt->double_q;
+    head.weighted = opt->weighted;
+  }
   StepRequest r{};
   r.slots = iw;
   r.gout = word;
@@ -1242,9 +1301,8 @@ static int wide_debug_check(WideKind kind, int batch, unsigned request) {
   return check_step(&L, &P, &S, r);
 }
 
-extern "C" {
-
-int dqz_c51_create(const dqz_learner_config* cfg, int num_atoms, const float* support, dqz_c51** out) {
+static int c51_create(const dqz_learner_config* cfg, int num_atoms, const float* support,
+                      const dqz_wide_options* opt, dqz_c51** out) {
   if (!cfg || !support || !out) return fail(DQZ_ERR_INVALID, "null argument");
   if (int rc = wide_check_config(WIDE_C51, cfg, num_atoms)) return rc;
   // the support, checked on the host (this call may synchronise; the step never does)
@@ -1253,11 +1311,11 @@ int dqz_c51_create(const dqz_learner_config* cfg, int num_atoms, const float* su
   for (int i = 0; i < num_atoms; ++i)
     if (!std::isfinite(z[i]) || (i > 0 && !(z[i] > z[i - 1])))
       return fail(DQZ_ERR_INVALID, "support must be finite and strictly increasing (atom %d)", i);
-  return wide_create(WIDE_C51, cfg, num_atoms, z, 0.f, reinterpret_cast<dqz_wide**>(out));
+  return wide_create(WIDE_C51, cfg, num_atoms, z, 0.f, opt, reinterpret_cast<dqz_wide**>(out));
 }
 
-int dqz_qr_create(const dqz_learner_config* cfg, int num_quantiles, const float* quantiles, float huber_param,
-                  dqz_qr** out) {
+static int qr_create(const dqz_learner_config* cfg, int num_quantiles, const float* quantiles, float huber_param,
+                     const dqz_wide_options* opt, dqz_qr** out) {
   if (!cfg || !quantiles || !out) return fail(DQZ_ERR_INVALID, "null argument");
   if (int rc = wide_check_config(WIDE_QR, cfg, num_quantiles)) return rc;
   if (!std::isfinite(huber_param) || !(huber_param > 0.f))
@@ -1270,7 +1328,28 @@ int dqz_qr_create(const dqz_learner_config* cfg, int num_quantiles, const float*
   for (int i = 0; i < num_quantiles; ++i)
     if (!std::isfinite(tau[i]) || !(tau[i] > 0.f && tau[i] < 1.f))
       return fail(DQZ_ERR_INVALID, "quantiles must be finite and strictly inside (0, 1) (quantile %d)", i);
-  return wide_create(WIDE_QR, cfg, num_quantiles, tau, huber_param, reinterpret_cast<dqz_wide**>(out));
+  return wide_create(WIDE_QR, cfg, num_quantiles, tau, huber_param, opt, reinterpret_cast<dqz_wide**>(out));
+}
+
+extern "C" {
+
+int dqz_c51_create(const dqz_learner_config* cfg, int num_atoms, const float* support, dqz_c51** out) {
+  return c51_create(cfg, num_atoms, support, nullptr, out);
+}
+int dqz_c51_create_opt(const dqz_learner_config* cfg, int num_atoms, const float* support,
+                       const dqz_wide_options* options, dqz_c51** out) {
+  if (int rc = wide_check_options(options)) return rc;
+  return c51_create(cfg, num_atoms, support, options, out);
+}
+
+int dqz_qr_create(const dqz_learner_config* cfg, int num_quantiles, const float* quantiles, float huber_param,
+                  dqz_qr** out) {
+  return qr_create(cfg, num_quantiles, quantiles, huber_param, nullptr, out);
+}
+int dqz_qr_create_opt(const dqz_learner_config* cfg, int num_quantiles, const float* quantiles, float huber_param,
+                      const dqz_wide_options* options, dqz_qr** out) {
+  if (int rc = wide_check_options(options)) return rc;
+  return qr_create(cfg, num_quantiles, quantiles, huber_param, options, out);
 }
 
 int dqz_c51_param_layout(int num_actions, int num_atoms, int64_t offsets[10], int64_t sizes[10], int64_t* total) {
@@ -1283,19 +1362,37 @@ int dqz_c51_destroy(dqz_c51* C) { return wide_destroy(wide_of(C)); }
 int dqz_c51_learner(dqz_c51* C, dqz_learner** out) { return wide_learner(wide_of(C), out); }
 int dqz_c51_step(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, dqz_optimizer* o,
                  int32_t* count, void* stream) {
-  return wide_step(wide_of(C), P, S, slots, o, count, stream);
+  return wide_step(wide_of(C), P, S, slots, nullptr, o, count, stream);
+}
+int dqz_c51_step_w(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, const float* is_weights,
+                   dqz_optimizer* o, int32_t* count, void* stream) {
+  if (int rc = wide_check_weights(C, is_weights)) return rc;
+  return wide_step(wide_of(C), P, S, slots, is_weights, o, count, stream);
 }
 int dqz_c51_grad(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
                  void* stream) {
-  return wide_grad(wide_of(C), P, S, slots, grad_out, stream);
+  return wide_grad(wide_of(C), P, S, slots, nullptr, grad_out, stream);
+}
+int dqz_c51_grad_w(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, const float* is_weights,
+                   float* grad_out, void* stream) {
+  if (int rc = wide_check_weights(C, is_weights)) return rc;
+  return wide_grad(wide_of(C), P, S, slots, is_weights, grad_out, stream);
 }
 int dqz_c51_profile(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
                     int iters, float* phase_ms, void* stream) {
-  return wide_profile(wide_of(C), P, S, slots, grad_out, iters, phase_ms, stream);
+  return wide_profile(wide_of(C), P, S, slots, nullptr, grad_out, iters, phase_ms, stream);
+}
+int dqz_c51_profile_w(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots,
+                      const float* is_weights, float* grad_out, int iters, float* phase_ms, void* stream) {
+  if (int rc = wide_check_weights(C, is_weights)) return rc;
+  return wide_profile(wide_of(C), P, S, slots, is_weights, grad_out, iters, phase_ms, stream);
 }
 int dqz_c51_outputs(dqz_c51* C, float* logits_a, float* q_values, float* loss_b, float* loss, int32_t* a_star,
                     void* stream) {
   return wide_outputs(wide_of(C), logits_a, q_values, loss_b, loss, a_star, stream);
+}
+int dqz_c51_outputs_opt(dqz_c51* C, float* q_selector, float* priorities, void* stream) {
+  return wide_outputs_opt(wide_of(C), q_selector, priorities, stream);
 }
 int dqz_c51_debug(dqz_c51* C, float* logits, float* dlogits, void* stream) {
   return wide_debug(wide_of(C), logits, dlogits, stream);
@@ -1311,7 +1408,11 @@ int dqz_c51_act(dqz_c51* C, const float* params, const uint8_t* states, int n, d
                 uint64_t counter, dqz_action* out, void* stream) {
   return wide_act(wide_of(C), params, states, n, epsilon, seed, counter, out, stream);
 }
-int dqz_c51_debug_check(int batch, unsigned request) { return wide_debug_check(WIDE_C51, batch, request); }
+int dqz_c51_debug_check(int batch, unsigned request) { return wide_debug_check(WIDE_C51, batch, request, nullptr); }
+int dqz_c51_debug_check_opt(int batch, unsigned request, const dqz_wide_options* options) {
+  if (int rc = wide_check_options(options)) return rc;
+  return wide_debug_check(WIDE_C51, batch, request, options);
+}
 
 int dqz_qr_param_layout(int num_actions, int num_quantiles, int64_t offsets[10], int64_t sizes[10], int64_t* total) {
   return wide_layout(WIDE_QR, num_actions, num_quantiles, offsets, sizes, total);
@@ -1323,19 +1424,37 @@ int dqz_qr_destroy(dqz_qr* Q) { return wide_destroy(wide_of(Q)); }
 int dqz_qr_learner(dqz_qr* Q, dqz_learner** out) { return wide_learner(wide_of(Q), out); }
 int dqz_qr_step(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, dqz_optimizer* o,
                 int32_t* count, void* stream) {
-  return wide_step(wide_of(Q), P, S, slots, o, count, stream);
+  return wide_step(wide_of(Q), P, S, slots, nullptr, o, count, stream);
+}
+int dqz_qr_step_w(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, const float* is_weights,
+                   dqz_optimizer* o, int32_t* count, void* stream) {
+  if (int rc = wide_check_weights(Q, is_weights)) return rc;
+  return wide_step(wide_of(Q), P, S, slots, is_weights, o, count, stream);
 }
 int dqz_qr_grad(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
                 void* stream) {
-  return wide_grad(wide_of(Q), P, S, slots, grad_out, stream);
+  return wide_grad(wide_of(Q), P, S, slots, nullptr, grad_out, stream);
+}
+int dqz_qr_grad_w(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, const float* is_weights,
+                   float* grad_out, void* stream) {
+  if (int rc = wide_check_weights(Q, is_weights)) return rc;
+  return wide_grad(wide_of(Q), P, S, slots, is_weights, grad_out, stream);
 }
 int dqz_qr_profile(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
                    int iters, float* phase_ms, void* stream) {
-  return wide_profile(wide_of(Q), P, S, slots, grad_out, iters, phase_ms, stream);
+  return wide_profile(wide_of(Q), P, S, slots, nullptr, grad_out, iters, phase_ms, stream);
+}
+int dqz_qr_profile_w(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots,
+                      const float* is_weights, float* grad_out, int iters, float* phase_ms, void* stream) {
+  if (int rc = wide_check_weights(Q, is_weights)) return rc;
+  return wide_profile(wide_of(Q), P, S, slots, is_weights, grad_out, iters, phase_ms, stream);
 }
 int dqz_qr_outputs(dqz_qr* Q, float* theta, float* q_values, float* loss_b, float* loss, int32_t* a_star,
                    void* stream) {
   return wide_outputs(wide_of(Q), theta, q_values, loss_b, loss, a_star, stream);
+}
+int dqz_qr_outputs_opt(dqz_qr* Q, float* q_selector, float* priorities, void* stream) {
+  return wide_outputs_opt(wide_of(Q), q_selector, priorities, stream);
 }
 int dqz_qr_debug(dqz_qr* Q, float* outputs, float* dtheta, void* stream) {
   return wide_debug(wide_of(Q), outputs, dtheta, stream);
@@ -1351,7 +1470,11 @@ int dqz_qr_act(dqz_qr* Q, const float* params, const uint8_t* states, int n, dou
                uint64_t counter, dqz_action* out, void* stream) {
   return wide_act(wide_of(Q), params, states, n, epsilon, seed, counter, out, stream);
 }
-int dqz_qr_debug_check(int batch, unsigned request) { return wide_debug_check(WIDE_QR, batch, request); }
+int dqz_qr_debug_check(int batch, unsigned request) { return wide_debug_check(WIDE_QR, batch, request, nullptr); }
+int dqz_qr_debug_check_opt(int batch, unsigned request, const dqz_wide_options* options) {
+  if (int rc = wide_check_options(options)) return rc;
+  return wide_debug_check(WIDE_QR, batch, request, options);
+}
 
 }  // extern "C"
 

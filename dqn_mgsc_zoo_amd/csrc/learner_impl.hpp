@@ -239,13 +239,19 @@ struct WideHead {
   int N;              // atoms / quantiles per action
   const float* grid;  // [N] device: the support, strictly increasing / tau, each strictly inside (0, 1)
   float kappa;        // huber_param > 0 (quantile head only)
-  float* out;         // [2][B][A N] online(s_tm1), target(s_t): logits / quantile outputs
+  float* out;         // [Z][B][A N] online(s_tm1), target(s_t) and, with double_q, online(s_t): logits / quantile
+                      // outputs (Z is the inner learner's: 2, or 3 with double_q)
   float* taken;       // [B][N] online outputs of the taken action (la / theta)
   float* dtaken;      // [B][N] d loss / d those outputs (dl / dtheta)
   float* dout;        // [B][A N] (+ QR_PAD) the dense cotangent of the online outputs; null for the categorical
                       // head, whose head kernel writes dz1 itself
-  float* qv;          // [2][B][A] q_values
-  int32_t* astar;     // [B] argmax_a q_values of the target copy
+  float* qv;          // [Z][B][A] q_values
+  int32_t* astar;     // [B] argmax_a q_values of the target copy (double_q: of the third copy, the selector)
+  // dqz_c51_create_opt / dqz_qr_create_opt (dqz_wide_options); both 0 in a head of the plain creates
+  int double_q;       // the inner learner runs three copies (DQZ_ALGO_DOUBLE's Z) and copy 2 selects a*
+  int weighted;       // every step takes is_weights [B]; the head writes clip(|loss_b|, 0, 100) to the learner's td
+  float* loss_b;      // [B] the unweighted per-sample loss of a weighted head (the learner's loss_part then holds
+                      // w_b loss_b, what the update sums); null otherwise
 };
 constexpr int C51_MAX_ATOMS = 64, C51_MAX_OUT = 1024;     // c51.hpp's C51_MAXN / C51_MAXOUT
 constexpr int QR_MAX_QUANTILES = 256, QR_MAX_OUT = 4096;  // qr.hpp's QR_MAXN / QR_MAXOUT

@@ -211,7 +211,10 @@ int dqz::check_step(const dqz_learner* L, const dqz_params* P, const dqz_store* 
   if (!!r.draw + !!r.sm + !!r.smx + !!r.pd > 1) return fail(DQZ_ERR_INVALID, "a step takes at most one batch draw");
   if (r.wide) {  // a wide head: what it does not take, each by name (kWide words what the two say differently)
     const WideDesc& d = kWide[r.wide->kind];
-    if (r.is_weights) return fail(DQZ_ERR_INVALID, "the %s head takes no importance weights", d.noun);
+    if (r.is_weights && !r.wide->weighted)
+      return fail(DQZ_ERR_INVALID, "the %s head takes no importance weights", d.noun);
+    if (r.wide->weighted && !r.is_weights)
+      return fail(DQZ_ERR_INVALID, "a weighted %s step needs is_weights", d.noun);
     if (r.pd) return fail(DQZ_ERR_INVALID, "the %s head takes no prioritized draw", d.noun);
     if (r.draw || r.sm || r.smx) return fail(DQZ_ERR_INVALID, "the %s head takes no in-launch batch draw", d.noun);
     if (r.meta_p || r.meta_epi || r.meta_sm) return fail(DQZ_ERR_INVALID, "%s", d.no_meta);
@@ -219,7 +222,9 @@ int dqz::check_step(const dqz_learner* L, const dqz_params* P, const dqz_store* 
     if (r.wb) return fail(DQZ_ERR_INVALID, "%s", d.no_wb);
     if (!r.gout) return fail(DQZ_ERR_INVALID, "%s", d.no_fused);
     if (L->cfg.batch == 1) return fail(DQZ_ERR_INVALID, "the %s head needs batch >= 2", d.noun);
-    if (L->cfg.algo != DQZ_ALGO_DQN) return fail(DQZ_ERR_INVALID, "the %s head runs on a DQN learner", d.noun);
+    // a double_q head's inner learner is the three-copy one; no other algo stands behind a wide head
+    if (L->cfg.algo != (r.wide->double_q ? DQZ_ALGO_DOUBLE : DQZ_ALGO_DQN))
+      return fail(DQZ_ERR_INVALID, "the %s head runs on a DQN learner", d.noun);
   }
   return DQZ_OK;
 }

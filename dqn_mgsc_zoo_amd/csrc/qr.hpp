@@ -17,7 +17,14 @@
 //                      the N x N quantile-Huber sum (thread (i, s) walks the
 //                      s-th quarter of j in order), dtheta, the loss and dout.
 //                      Forward / actor mode stops after q_values (and the
-//                      eps-greedy draw).
+//                      eps-greedy draw).  WIDE_DOUBLE (c51.hpp): a* comes from
+//                      a third copy, online(s_t) (rlax.quantile_q_learning
+//                      with dist_q_t_selector = online(s_t)); WIDE_WEIGHTED:
+//                      dtheta carries the sample's importance weight and
+//                      clip(|loss_b|, 0, 100) is its new priority.  The
+//                      reference has no prioritized QR-DQN: the quantile
+//                      priority is this project's definition, Rainbow's rule
+//                      (rainbow/agent.py:198) on the quantile loss.
 //   qr_dz1_kernel      dz1[16 samples][16 rows] = dout[16][A N] W2^T[A N][16]
 //                      on v_mfma_f32_16x16x4_f32, K dealt to the workgroup's
 //                      eight waves and added in wave order, then copy 0's ReLU
@@ -27,6 +34,7 @@
 //                      from the batch), summed in sample order.
 #pragma once
 #include "common.hpp"
+#include "c51.hpp"   // WIDE_DOUBLE, WIDE_WEIGHTED, WIDE_MAX_PRIORITY
 #include "head.hpp"  // eps_greedy
 
 namespace dqz {
@@ -48,14 +56,18 @@ struct QrHeadArgs {
   float* theta;       // [B][N] online outputs of the taken action
   float* dtheta;      // [B][N] d loss / d those outputs
   float* dout;        // [B][A N] the dense cotangent: dtheta at column i A + a_b, zeros elsewhere
-  int32_t* astar;     // [B] argmax_a q_target
-  float* loss_part;   // [B]
+  int32_t* astar;     // [B] argmax_a q_target (WIDE_DOUBLE: of copy 2's q_values)
+  float* loss_part;   // [B] what the update sums to the step's loss: loss_b (WIDE_WEIGHTED: w_b loss_b)
   float* gq;          // [B] <- 0 (the scalar head's cotangent: unused downstream, never stale)
   int32_t* ga;        // [B] <- a_b
   // actor mode (fwd_only): eps-greedy draw per sample into act_out (or null)
   dqz_action* act_out;
   double eps;
   uint64_t act_seed, act_ctr;
+  // WIDE_WEIGHTED alone (last, so that the plain kernels read their arguments where they always did)
+  const float* weights;  // [B] importance weights
+  float* loss_b;         // [B] the unweighted per-sample loss
+  float* prio;           // [B] clip(|loss_b|, 0, 100): the learner's td buffer, which dqz_per_write_back reads
 };
 
 // One workgroup (1024 threads) per sample b.  Every global load (the record,
@@ -65,24 +77,31 @@ struct QrHeadArgs {
 // quantile are added in s order, the loss rows in i order, so equal inputs give
 // equal bits.  The target t_j is a broadcast LDS read.  The N^2 pairs are the
 // launch's arithmetic: about six instructions a pair on one CU's four SIMDs.
+// With WIDE_DOUBLE copy 2's outputs never enter LDS (the two copies there fill
+// its 32 KB): the wave that owns an action of it sums the action's quantiles
+// from global memory, in the order the other copies' are summed.  MODE = 0
+// compiles to the instructions the kernel had before it took a mode.
+template <int MODE>
 DQZ_OTHER_KERNEL __launch_bounds__(QR_THREADS) void qr_head_kernel(QrHeadArgs h) {
+  constexpr bool DQ = MODE & WIDE_DOUBLE, WT = MODE & WIDE_WEIGHTED;
   __shared__ float s_x[2 * QR_MAXOUT];  // copy z's outputs at [z A N, (z + 1) A N)
   __shared__ __attribute__((aligned(8))) float s_t[QR_MAXN];
   __shared__ float s_th[QR_MAXN], s_g[QR_MAXN];
   __shared__ float s_lp[QR_JS][QR_MAXN], s_gp[QR_JS][QR_MAXN];
-  __shared__ float s_q[2][MAXA];
+  __shared__ float s_q[DQ ? 3 : 2][MAXA];
   const int b = blockIdx.x, n = threadIdx.x, lane = n & 63, wave = n >> 6;
-  const int A = h.A, N = h.N, AN = A * N, B = h.B, Z = h.Z, tot = Z * AN;
+  const int A = h.A, N = h.N, AN = A * N, B = h.B, Z = h.Z, tot = (DQ ? 2 : Z) * AN;  // tot: the copies held in LDS
   const int qi = n & (QR_MAXN - 1), qic = min(qi, N - 1);
   const int qs = __builtin_amdgcn_readfirstlane(n / QR_MAXN);  // a wave lies inside one j range: scalar loop bounds
   int a_tm1 = 0;
-  float r = 0.f, d = 0.f, tau = 0.5f;
+  float r = 0.f, d = 0.f, tau = 0.5f, wt = 1.f;
   if (!h.fwd_only) {
     const float4 rv = h.rec[b];
     a_tm1 = min(max(__float_as_int(rv.x), 0), A - 1);  // a record outside [0, A) reads inside the buffers
     r = rv.y;
     d = rv.z;
     tau = h.tau[qic];
+    if (WT) wt = h.weights[b];
   }
   {
     float v[QR_LOADS];
@@ -100,7 +119,12 @@ DQZ_OTHER_KERNEL __launch_bounds__(QR_THREADS) void qr_head_kernel(QrHeadArgs h)
   for (int row = wave; row < Z * A; row += QR_THREADS / 64) {
     const int z = row / A, a = row % A;
     float acc = 0.f;
-    for (int i = lane; i < N; i += 64) acc += s_x[z * AN + i * A + a];
+    if (DQ && z == 2) {  // wave-uniform
+      const float* x2 = h.out + ((int64_t)2 * B + b) * AN + a;
+      for (int i = lane; i < N; i += 64) acc += x2[i * A];
+    } else {
+      for (int i = lane; i < N; i += 64) acc += s_x[z * AN + i * A + a];
+    }
     const float q = wave_sum(acc) / (float)N;
     if (lane == 0) {
       s_q[z][a] = q;
@@ -119,10 +143,11 @@ DQZ_OTHER_KERNEL __launch_bounds__(QR_THREADS) void qr_head_kernel(QrHeadArgs h)
   }
   int am = 0;  // jnp.argmax: first maximum; every thread forms it from the same LDS values
   {
-    float best = s_q[1][0];
+    const float* sel = s_q[DQ ? 2 : 1];
+    float best = sel[0];
     for (int a = 1; a < A; ++a)
-      if (s_q[1][a] > best) {
-        best = s_q[1][a];
+      if (sel[a] > best) {
+        best = sel[a];
         am = a;
       }
   }
@@ -166,7 +191,8 @@ DQZ_OTHER_KERNEL __launch_bounds__(QR_THREADS) void qr_head_kernel(QrHeadArgs h)
       ls += s_lp[s][n];
       gs += s_gp[s][n];
     }
-    const float g = -(gs / (float)(N * B));
+    float g = -(gs / (float)(N * B));
+    if (WT) g = wt == 0.f ? 0.f : g * wt;  // a weight of 0: +0.0, whatever g's sign
     s_g[n] = g;
     s_lp[0][n] = ls / (float)N;  // the row's mean over j; this thread alone reads and writes column n
     h.theta[(int64_t)b * N + n] = s_th[n];
@@ -180,7 +206,13 @@ DQZ_OTHER_KERNEL __launch_bounds__(QR_THREADS) void qr_head_kernel(QrHeadArgs h)
   if (n == 0) {
     float loss = 0.f;
     for (int i = 0; i < N; ++i) loss += s_lp[0][i];
-    h.loss_part[b] = loss;
+    if (WT) {
+      h.loss_part[b] = wt * loss;
+      h.loss_b[b] = loss;
+      h.prio[b] = fminf(fabsf(loss), WIDE_MAX_PRIORITY);
+    } else {
+      h.loss_part[b] = loss;
+    }
     h.gq[b] = 0.f;
     h.ga[b] = a_tm1;
     h.astar[b] = am;

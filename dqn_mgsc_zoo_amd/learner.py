@@ -558,7 +558,8 @@ def _wide_entries(prefix):
   """_ENTRIES of a wide head: every entry is `prefix` + its own name."""
   return {e: prefix + e for e in (
       'create', 'learner', 'optimizer_create', 'destroy', 'step', 'grad',
-      'outputs', 'debug', 'profile', 'forward', 'forward_slots', 'act')}
+      'outputs', 'debug', 'profile', 'forward', 'forward_slots', 'act',
+      'create_opt', 'step_w', 'grad_w', 'profile_w', 'outputs_opt')}
 
 
 class _WideLearner(Learner):
@@ -569,7 +570,15 @@ class _WideLearner(Learner):
   sync_status, grad_norm); the step is the learner step with the wide head, in
   gradient mode, followed by the optimizer, so the optimizer is Adam or plain
   RMSProp, alone or behind clip_by_global_norm (the reference's chain is the
-  default)."""
+  default).
+
+  double_q / prioritized (dqz_wide_options): Rainbow's learning rule on the
+  same network.  double_q selects a* with the online network at s_t, a third
+  copy whose q_values are `q[2]`.  prioritized makes every step take the
+  replay's importance `weights` [B]: the loss is mean(w loss_b), loss_b stays
+  unweighted, and `priorities` [B] = clip(|loss_b|, 0, 100) are also what
+  dqz_per_write_back on this learner's inner handle writes to the sum tree.
+  With both off the old create entry is called and nothing differs."""
 
   _wide = None  # the head's handle (dqz_c51 / dqz_qr); it owns the dqz_learner behind _h
   _OWNER = '_wide'
@@ -582,7 +591,8 @@ class _WideLearner(Learner):
   _ALGO = _TITLE = _HEAD = None  # `algo`, and the head's names in messages
   _PROFILE_SLOTS = None  # profile(): phase slot -> the head's launch there
 
-  def __init__(self, network, batch_size, optimizer, device, *head_args):
+  def __init__(self, network, batch_size, optimizer, device, *head_args,
+               double_q=False, prioritized=False):
     if not isinstance(network, self._SPEC):
       raise ValueError('%s needs networks.%s' % (self._CLASS, self._NETWORK))
     head_args = self._check_head_args(*head_args)
@@ -602,14 +612,24 @@ class _WideLearner(Learner):
     grid = torch.from_numpy(getattr(network, self._GRID)).to(self.device)
     setattr(self, self._GRID, grid)
     setattr(self, self._TAKEN, torch.zeros((b, n), **f32))
-    self.q = torch.zeros((2, b, a), **f32)
+    self.double_q, self.prioritized = bool(double_q), bool(prioritized)
+    self.copies = 3 if self.double_q else 2
+    self.q = torch.zeros((self.copies, b, a), **f32)
+    self.priorities = torch.zeros((b,), **f32) if self.prioritized else None
     self.loss_b = torch.zeros((b,), **f32)
     self.loss = torch.zeros((1,), **f32)
     self.a_star = torch.zeros((b,), dtype=torch.int32, device=self.device)
     handle = ctypes.c_void_p()
-    _native.check(self._entry('create')(
-        ctypes.byref(self._learner_config(_native.ALGO_DQN)), n,
-        _native.ptr(grid), *head_args, ctypes.byref(handle)))
+    if self.double_q or self.prioritized:
+      options = _native.DqzWideOptions(int(self.double_q), int(self.prioritized))
+      _native.check(self._entry('create_opt')(
+          ctypes.byref(self._learner_config(_native.ALGO_DQN)), n,
+          _native.ptr(grid), *head_args, ctypes.byref(options),
+          ctypes.byref(handle)))
+    else:
+      _native.check(self._entry('create')(
+          ctypes.byref(self._learner_config(_native.ALGO_DQN)), n,
+          _native.ptr(grid), *head_args, ctypes.byref(handle)))
     self._wide = handle
     inner = ctypes.c_void_p()
     _native.check(self._call('learner', ctypes.byref(inner)))
@@ -634,57 +654,85 @@ class _WideLearner(Learner):
           'optimizer is %s)' % (self._TITLE, type(self.base_optimizer).__name__))
     super().load_opt_state(state)
 
-  def step(self, store, slots, stream=None):  # pylint: disable=arguments-differ
-    """One learner step on replay `slots` (device int32 [B])."""
+  def _weighted_args(self, slots, weights):
+    """(entry suffix, arguments behind the store) of a step on `slots`: a
+    prioritized learner takes `weights` (device f32 [B]), another none."""
     self._check_slots(slots)
+    if not self.prioritized:
+      if weights is not None:
+        raise ValueError(
+            'this %s takes no importance weights: create it with '
+            'prioritized=True' % self._CLASS)
+      return '', (_native.ptr(slots),)
+    if weights is None:
+      raise ValueError('a prioritized %s step needs importance weights'
+                       % self._CLASS)
+    if (weights.dtype != torch.float32 or weights.numel() != self.batch_size or
+        not weights.is_contiguous() or not weights.is_cuda):
+      raise ValueError('weights must be a device float32 tensor of batch size')
+    return '_w', (_native.ptr(slots), _native.ptr(weights))
+
+  def step(self, store, slots, weights=None, stream=None):  # pylint: disable=arguments-differ
+    """One learner step on replay `slots` (device int32 [B]); a prioritized
+    learner's also takes the importance `weights` (device f32 [B])."""
+    suffix, args = self._weighted_args(slots, weights)
     _native.check(self._call(
-        'step', ctypes.byref(self._params_c), store.c_ref(), _native.ptr(slots),
+        'step' + suffix, ctypes.byref(self._params_c), store.c_ref(), *args,
         self._opt_h, _native.ptr(self.count), _native.stream_handle(stream)))
 
-  def grad(self, store, slots, out=None, stream=None):  # pylint: disable=arguments-differ
+  def grad(self, store, slots, weights=None, out=None, stream=None):  # pylint: disable=arguments-differ
     """jax.grad(loss_fn) of the same step into a flat tensor (no update).
     Every element of every leaf is written; the padding floats between the
     leaves and behind the last keep what `out` held (zeros in the tensor
     allocated here)."""
-    self._check_slots(slots)
+    suffix, args = self._weighted_args(slots, weights)
     out = torch.zeros_like(self.online) if out is None else out
     _native.check(self._call(
-        'grad', ctypes.byref(self._params_c), store.c_ref(), _native.ptr(slots),
+        'grad' + suffix, ctypes.byref(self._params_c), store.c_ref(), *args,
         _native.ptr(out), _native.stream_handle(stream)))
     return out
 
   def fetch_outputs(self, stream=None):
     """(outputs of the taken action [B,N], q_values [2,B,A] of online(s_tm1)
     and target(s_t), per-sample loss [B], mean loss [1], the target's greedy
-    action [B]) of the last step, copied into self tensors."""
+    action [B]) of the last step, copied into self tensors.  With double_q,
+    q_values is [3,B,A] (the third block: online(s_t), the selector) and the
+    action is the selector's; a prioritized learner's tuple ends in the
+    priorities [B].  The per-sample loss is unweighted, the mean weighted."""
     taken = getattr(self, self._TAKEN)
     _native.check(self._call(
         'outputs', _native.ptr(taken), _native.ptr(self.q),
         _native.ptr(self.loss_b), _native.ptr(self.loss),
         _native.ptr(self.a_star), _native.stream_handle(stream)))
-    return taken, self.q, self.loss_b, self.loss, self.a_star
+    out = (taken, self.q, self.loss_b, self.loss, self.a_star)
+    if self.double_q or self.prioritized:
+      _native.check(self._call(
+          'outputs_opt', _native.ptr(self.q[2]) if self.double_q else None,
+          _native.ptr(self.priorities), _native.stream_handle(stream)))
+    return out + (self.priorities,) if self.prioritized else out
 
   def fetch_head(self, stream=None):
-    """Diagnostic: the last step's outputs of both copies (_out_shape) and
-    the cotangent [B,N] of the taken action's."""
+    """Diagnostic: the last step's outputs of every copy (_out_shape; three
+    with double_q) and the cotangent [B,N] of the taken action's."""
     b, a = self.batch_size, self.network.num_actions
     n = getattr(self.network, self._COUNT)
-    out = torch.empty(self._out_shape(b, a, n), dtype=torch.float32,
+    shape = (self.copies,) + tuple(self._out_shape(b, a, n))[1:]
+    out = torch.empty(shape, dtype=torch.float32,
                       device=self.device)
     dtaken = torch.empty((b, n), dtype=torch.float32, device=self.device)
     _native.check(self._call('debug', _native.ptr(out), _native.ptr(dtaken),
                              _native.stream_handle(stream)))
     return out, dtaken
 
-  def profile(self, store, slots, iters=20, stream=None):  # pylint: disable=arguments-differ
+  def profile(self, store, slots, weights=None, iters=20, stream=None):  # pylint: disable=arguments-differ
     """Average ms per launch (the head's profile entry), dict; the gradient
     goes to a scratch tensor and no parameter changes."""
-    self._check_slots(slots)
+    suffix, args = self._weighted_args(slots, weights)
     out = (ctypes.c_float * _native.NUM_PHASES)()
     scratch = torch.zeros_like(self.online)
     _native.check(self._call(
-        'profile', ctypes.byref(self._params_c), store.c_ref(),
-        _native.ptr(slots), _native.ptr(scratch), int(iters), out,
+        'profile' + suffix, ctypes.byref(self._params_c), store.c_ref(),
+        *args, _native.ptr(scratch), int(iters), out,
         _native.stream_handle(stream)))
     names = list(_native.PHASE_NAMES)
     for slot, name in self._PROFILE_SLOTS.items():
@@ -715,8 +763,10 @@ class C51Learner(_WideLearner):
   _c51 = property(lambda self: self._wide)
 
   def __init__(self, network: networks_lib.C51NetworkSpec, batch_size,
-               optimizer=None, device='cuda'):
-    super().__init__(network, batch_size, optimizer, device)
+               optimizer=None, device='cuda', double_q=False,
+               prioritized=False):
+    super().__init__(network, batch_size, optimizer, device,
+                     double_q=double_q, prioritized=prioritized)
 
   def _out_shape(self, b, a, n):
     return (2, b, a, n)  # q_logits
@@ -752,8 +802,10 @@ class QrLearner(_WideLearner):
   _qr = property(lambda self: self._wide)
 
   def __init__(self, network: networks_lib.QRNetworkSpec, batch_size,
-               huber_param=1.0, optimizer=None, device='cuda'):
-    super().__init__(network, batch_size, optimizer, device, huber_param)
+               huber_param=1.0, optimizer=None, device='cuda', double_q=False,
+               prioritized=False):
+    super().__init__(network, batch_size, optimizer, device, huber_param,
+                     double_q=double_q, prioritized=prioritized)
 
   def _check_head_args(self, huber_param):  # pylint: disable=arguments-differ
     self.huber_param = check_huber_param(huber_param)

@@ -1269,3 +1269,64 @@ class TransitionAccumulator:
   def reset(self) -> None:
     self._timestep_tm1 = None
     self._a_tm1 = None
+
+
+# ---------------------------------------------------------------------------
+# timesteps -> n-step transitions (replay.py:1200-1285)
+
+
+def n_step_transition(steps) -> Transition:
+  """One transition from consecutive 1-step ones: the first's s_tm1 and a_tm1,
+  the last's s_t, r = sum_k (prod_{i<k} d_i) r_k and d = prod_k d_k, summed and
+  multiplied in step order from 0.0 and 1.0 (replay.py:1200-1215)."""
+  r_t, discount_t = 0.0, 1.0
+  for step in steps:
+    r_t += discount_t * step.r_t
+    discount_t *= step.discount_t
+  return Transition(s_tm1=steps[0].s_tm1, a_tm1=steps[0].a_tm1, r_t=r_t,
+                    discount_t=discount_t, s_t=steps[-1].s_t)
+
+
+class NStepTransitionAccumulator:
+  """Pairs the timesteps of an episode into n-step transitions.
+
+  FIRST yields nothing.  A MID timestep t yields s_{t-n} -> s_t once n 1-step
+  transitions are held, nothing before.  LAST (t = T) yields every transition
+  that ends at s_T, from min(n, T) steps down to 1.  The states are the
+  timesteps' own observation objects, so a device replay's frame allocator
+  finds each stack's frames among those it has placed (s_tm1 and s_t lie n
+  frames apart, and an episode's last transitions share one s_t)."""
+
+  def __init__(self, n):
+    if int(n) != n or n < 1:
+      raise ValueError('n must be a positive integer, got %r.' % (n,))
+    self._n = int(n)
+    self._steps = collections.deque(maxlen=self._n)  # the last n 1-step transitions
+    self.reset()
+
+  def step(self, timestep_t, a_t) -> Iterable[Transition]:
+    if timestep_t.first():
+      self.reset()
+    if self._timestep_tm1 is None:
+      if not timestep_t.first():
+        raise ValueError('Expected FIRST timestep, got %s.' % str(timestep_t))
+      self._timestep_tm1 = timestep_t
+      self._a_tm1 = a_t
+      return
+    self._steps.append(Transition(
+        s_tm1=self._timestep_tm1.observation, a_tm1=self._a_tm1,
+        r_t=timestep_t.reward, discount_t=timestep_t.discount,
+        s_t=timestep_t.observation))
+    self._timestep_tm1 = timestep_t
+    self._a_tm1 = a_t
+    if timestep_t.last():
+      while self._steps:  # min(n, T)-step, ..., 1-step, all ending at s_T
+        yield n_step_transition(self._steps)
+        self._steps.popleft()
+    elif len(self._steps) == self._n:
+      yield n_step_transition(self._steps)
+
+  def reset(self) -> None:
+    self._steps.clear()
+    self._timestep_tm1 = None
+    self._a_tm1 = None

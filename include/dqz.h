@@ -752,6 +752,57 @@ int dqz_c51_act(dqz_c51* c51, const float* params, const uint8_t* states, int n,
 #define DQZ_C51_REQ_FUSED_RMSPROP 1024u /* no gradient output: the fused centered RMSProp */
 int dqz_c51_debug_check(int batch, unsigned request);
 
+/* ---- double-Q selection and importance weights on the wide heads ----------
+ * Rainbow's learning rule (rainbow/agent.py:85-150,198:
+ * rlax.categorical_double_q_learning, the loss weighted by the replay's
+ * importance weights, the clipped loss as the new priority) on the C51 and the
+ * QR-DQN networks, switched on when the head is created.
+ *   double_q  the forward runs a third copy, online parameters at s_t, and
+ *             a* = argmax_a q_values of that copy (first maximum).  The
+ *             categorical head then uses p = softmax(target logits)[a*], the
+ *             quantile head t_j = r + d x_target[j, a*]; nothing else in either
+ *             loss changes and no gradient flows through the third copy.
+ *             q_values is then [3][B][A]: dqz_*_outputs keeps returning the
+ *             first two blocks and a_star is the selector's choice;
+ *             dqz_*_debug returns the outputs of all three copies.
+ *   weighted  every step takes is_weights w [B] (the _w entries; the plain
+ *             step, grad and profile entries are refused, as a head without it
+ *             refuses the _w ones): loss = mean_b(w_b loss_b), d loss / d (taken
+ *             outputs) is the plain cotangent times w_b (a weight of exactly 0
+ *             gives +0.0 in every element), loss_b stays unweighted.  The head
+ *             also writes clip(|loss_b|, 0, 100) into the inner learner's TD
+ *             buffer, so dqz_per_write_back on the handle from dqz_c51_learner /
+ *             dqz_qr_learner writes the new priorities and the running maximum
+ *             into the device sum tree.  The reference has no prioritized
+ *             QR-DQN: the quantile priority is this library's definition,
+ *             Rainbow's rule applied to the quantile loss.
+ * A head with options still refuses, in the plain heads' words: the fused
+ * prioritized draw, every in-launch draw, the fused write-back, the MGSC
+ * modes, the unit cotangent, fused centered RMSProp and batch 1.  cfg->algo
+ * stays DQZ_ALGO_DQN: double_q makes the inner learner the three-copy one. */
+typedef struct dqz_wide_options {
+  int double_q; /* 0 or 1 */
+  int weighted; /* 0 or 1 */
+} dqz_wide_options;
+
+/* dqz_c51_create with options (non-null); {0, 0} is dqz_c51_create. */
+int dqz_c51_create_opt(const dqz_learner_config* cfg, int num_atoms, const float* support,
+                       const dqz_wide_options* options, dqz_c51** out);
+/* dqz_c51_step / _grad / _profile of a weighted head: is_weights device f32
+ * [B], refused before any device call when null. */
+int dqz_c51_step_w(dqz_c51* c51, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                   const float* is_weights, dqz_optimizer* opt, int32_t* count, void* stream);
+int dqz_c51_grad_w(dqz_c51* c51, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                   const float* is_weights, float* grad_out, void* stream);
+int dqz_c51_profile_w(dqz_c51* c51, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                      const float* is_weights, float* grad_out, int iters, float* phase_ms, void* stream);
+/* What the options add to dqz_c51_outputs (either may be NULL): q_selector
+ * [B][A], the third copy's q_values (double_q heads only); priorities [B],
+ * clip(|loss_b|, 0, 100) (weighted heads only). */
+int dqz_c51_outputs_opt(dqz_c51* c51, float* q_selector, float* priorities, void* stream);
+/* dqz_c51_debug_check for a head created with `options`. */
+int dqz_c51_debug_check_opt(int batch, unsigned request, const dqz_wide_options* options);
+
 /* ---- the quantile (QR-DQN) agent (qrdqn/agent.py:36-39,88-134) ------------
  * networks.qr_atari_network (networks.py:295-313): the NatureQNetwork torso
  * with a last layer N * A wide, N quantile values per action, quantile-major:
@@ -837,6 +888,19 @@ int dqz_qr_act(dqz_qr* qr, const float* params, const uint8_t* states, int n, do
 /* Diagnostic (tests): dqz_c51_debug_check for a quantile request; `request`
  * takes the DQZ_C51_REQ_* bits.  No device call. */
 int dqz_qr_debug_check(int batch, unsigned request);
+
+/* The quantile head with dqz_wide_options (above, at the categorical head's):
+ * the same entries, the same refusals. */
+int dqz_qr_create_opt(const dqz_learner_config* cfg, int num_quantiles, const float* quantiles, float huber_param,
+                      const dqz_wide_options* options, dqz_qr** out);
+int dqz_qr_step_w(dqz_qr* qr, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                  const float* is_weights, dqz_optimizer* opt, int32_t* count, void* stream);
+int dqz_qr_grad_w(dqz_qr* qr, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                  const float* is_weights, float* grad_out, void* stream);
+int dqz_qr_profile_w(dqz_qr* qr, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                     const float* is_weights, float* grad_out, int iters, float* phase_ms, void* stream);
+int dqz_qr_outputs_opt(dqz_qr* qr, float* q_selector, float* priorities, void* stream);
+int dqz_qr_debug_check_opt(int batch, unsigned request, const dqz_wide_options* options);
 
 /* PrioritizedTransitionReplay.add on device (replay.py:1068-1096 ->
  * PrioritizedDistribution.remove_priorities / add_priorities, :642-678): the

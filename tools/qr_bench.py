@@ -1,7 +1,7 @@
 """What the QR-DQN step costs beside the DQN and C51 steps with the same
 optimizer chain.
 
-usage (GPU box): python tools/qr_bench.py [--rounds R] [--reps N] [--capacity C] [--actions 6 18] > out.json
+usage (GPU box): python tools/qr_bench.py [--rounds R] [--reps N] [--capacity C] [--actions 6 18] [--double-q] [--prioritized] > out.json
 
 For each number of actions A (6 and 18), three learners at B = 32 on one
 synthetic replay, each a hipGraph of 20 learner steps (sample_uniform +
@@ -12,7 +12,10 @@ step on its slots) with chain(clip_by_global_norm(10), adam(5e-5, eps=0.01/32)):
 The arms are timed in the same process, interleaved round by round (arm order
 rotated), HIP events around N replays; the JSON gives each arm's median,
 minimum and maximum ms per step over the rounds and QR-DQN's difference to both
-other arms.
+other arms.  --double-q and --prioritized switch the c51 and qrdqn arms'
+learners to double-Q selection (a third network copy) and to
+importance-weighted steps (fixed uneven weights in (0, 1]; the priorities are
+written, the sum tree is not part of the arm).
 
 launch_us: dqz_qr_profile / dqz_c51_profile on a fixed batch, in a run of its
 own after the timed rounds: each launch of the step repeated back to back
@@ -41,14 +44,18 @@ def optimizer():
   return learner_lib.chain(learner_lib.clip_by_global_norm(10.0), learner_lib.adam(LR, eps=EPS))
 
 
-def make_arm(name, a, store, cap, dev):
+def make_arm(name, a, store, cap, dev, double_q=False, prioritized=False):
+  wide = dict(optimizer=optimizer(), device=dev, double_q=double_q, prioritized=prioritized)
+  weights = None
+  if prioritized and name != 'dqn_clip_adam_slots':
+    weights = torch.linspace(0.05, 1.0, B, dtype=torch.float32, device=dev)
   if name == 'qrdqn':
     tau = ((np.arange(N_QUANTILES, dtype=np.float32) + 0.5) / N_QUANTILES).astype(np.float32)
     net = networks.qr_atari_network(a, tau)
-    lrn = learner_lib.QrLearner(net, B, huber_param=KAPPA, optimizer=optimizer(), device=dev)
+    lrn = learner_lib.QrLearner(net, B, huber_param=KAPPA, **wide)
   elif name == 'c51':
     net = networks.c51_atari_network(a, np.linspace(-VMAX, VMAX, N_ATOMS).astype(np.float32))
-    lrn = learner_lib.C51Learner(net, B, optimizer=optimizer(), device=dev)
+    lrn = learner_lib.C51Learner(net, B, **wide)
   else:
     net = networks.dqn_atari_network(a)
     lrn = learner_lib.Learner(net, B, algo='dqn', optimizer=optimizer(), device=dev)
@@ -58,7 +65,7 @@ def make_arm(name, a, store, cap, dev):
 
   def fn():
     learner_lib.sample_uniform(0, cap, cap, B, 7, ctr, slots)
-    lrn.step(store, slots)
+    lrn.step(store, slots, weights)
   for _ in range(20):
     fn()
   torch.cuda.synchronize(dev)
@@ -71,7 +78,7 @@ def make_arm(name, a, store, cap, dev):
   with torch.cuda.graph(g):
     for _ in range(GRAPH_STEPS):
       fn()
-  return lrn, g, slots
+  return lrn, g, slots, weights
 
 
 def time_graph(g, reps, dev):
@@ -88,7 +95,7 @@ def time_graph(g, reps, dev):
 def run(a, args, dev):
   cap = args.capacity
   store = synthetic.fill_episodic(cap, a, seed=0, device=dev)
-  arms = {n: make_arm(n, a, store, cap, dev) for n in NAMES}
+  arms = {n: make_arm(n, a, store, cap, dev, args.double_q, args.prioritized) for n in NAMES}
   ms = {n: [] for n in NAMES}
   for r in range(args.rounds):
     for n in NAMES[r % 3:] + NAMES[:r % 3]:
@@ -105,8 +112,8 @@ def run(a, args, dev):
   # the launches' own durations, after the timed rounds (the profile synchronises between phases)
   out['launch_us'] = {}
   for n in ('qrdqn', 'c51'):
-    lrn, _, slots = arms[n]
-    out['launch_us'][n] = {k: round(1e3 * v, 2) for k, v in lrn.profile(store, slots, iters=50).items()}
+    lrn, _, slots, weights = arms[n]
+    out['launch_us'][n] = {k: round(1e3 * v, 2) for k, v in lrn.profile(store, slots, weights, iters=50).items()}
   net = networks.dqn_atari_network(a)
   dqn = learner_lib.Learner(net, B, algo='dqn', device=dev)  # the profile runs the fused-RMSProp step
   dqn.set_params(net.init(seed=1))
@@ -120,9 +127,11 @@ def main():
   ap.add_argument('--reps', type=int, default=100, help='graph replays (of 20 steps) per arm and round')
   ap.add_argument('--capacity', type=int, default=1_000_000)
   ap.add_argument('--actions', type=int, nargs='+', default=[6, 18])
+  ap.add_argument('--double-q', action='store_true', help='the c51 and qrdqn arms select a* with online(s_t)')
+  ap.add_argument('--prioritized', action='store_true', help='the c51 and qrdqn arms take importance weights')
   args = ap.parse_args()
   dev = torch.device('cuda:0')
-  out = {'batch': B, 'num_atoms': N_ATOMS, 'num_quantiles': N_QUANTILES, 'huber_param': KAPPA,
+  out = {'double_q': args.double_q, 'prioritized': args.prioritized, 'batch': B, 'num_atoms': N_ATOMS, 'num_quantiles': N_QUANTILES, 'huber_param': KAPPA,
          'capacity': args.capacity, 'graph_steps': GRAPH_STEPS,
          'steps_per_arm_and_round': args.reps * GRAPH_STEPS, 'rounds': args.rounds, 'by_num_actions': []}
   for a in args.actions:
