@@ -394,6 +394,36 @@ SIGNATURES['dqz_qr_create'] = (
     _int, [ctypes.POINTER(DqzLearnerConfig), _int, _vp, ctypes.c_float,
            ctypes.POINTER(_vp)])
 
+# The Rainbow agent's entries: the wide heads' with a noise buffer behind the
+# batch, always weighted (no plain / _w pair).
+RAINBOW_NUM_LEAVES = 20
+_P, _S = ctypes.POINTER(DqzParams), ctypes.POINTER(DqzStore)
+SIGNATURES.update({
+    'dqz_rainbow_param_layout': (
+        _int, [_int, _int, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+               ctypes.POINTER(_i64)]),
+    'dqz_rainbow_noise_len': (_int, [_int, _int, ctypes.POINTER(_int)]),
+    'dqz_rainbow_noise': (_int, [ctypes.c_uint64, _vp, _int, _vp, _vp]),
+    'dqz_rainbow_optimizer_create': _WIDE_SIGNATURES['optimizer_create'],
+    'dqz_rainbow_create': SIGNATURES['dqz_c51_create_opt'],
+    'dqz_rainbow_destroy': (_int, [_vp]),
+    'dqz_rainbow_learner': (_int, [_vp, ctypes.POINTER(_vp)]),
+    'dqz_rainbow_step': (_int, [_vp, _P, _S, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dqz_rainbow_grad': (_int, [_vp, _P, _S, _vp, _vp, _vp, _vp, _vp]),
+    'dqz_rainbow_profile': (
+        _int, [_vp, _P, _S, _vp, _vp, _vp, _vp, _int,
+               ctypes.POINTER(ctypes.c_float), _vp]),
+    'dqz_rainbow_outputs': _WIDE_SIGNATURES['outputs'],
+    'dqz_rainbow_outputs_opt': _WIDE_SIGNATURES['outputs_opt'],
+    'dqz_rainbow_debug_head': _WIDE_SIGNATURES['debug'],
+    'dqz_rainbow_debug': (_int, [_vp] * 8),
+    'dqz_rainbow_forward': (_int, [_vp, _vp, _vp, _int, _vp, _vp, _vp]),
+    'dqz_rainbow_forward_slots': (
+        _int, [_vp, _vp, _S, _vp, _int, _int, _vp, _vp, _vp]),
+    'dqz_rainbow_act': (_int, [_vp, _vp, _vp, _int, _vp, _vp, _vp]),
+    'dqz_rainbow_debug_check': (_int, [_int, ctypes.c_uint]),
+})
+
 _lib = None
 _lock = threading.Lock()
 
@@ -488,6 +518,25 @@ def c51_param_layout(num_actions, num_atoms):
 def qr_param_layout(num_actions, num_quantiles):
   """(offsets, sizes, total) of the quantile network's flat buffer."""
   return _layout('dqz_qr_param_layout', num_actions, num_quantiles)
+
+
+def rainbow_param_layout(num_actions, num_atoms):
+  """(offsets, sizes, total) of the Rainbow network's flat buffer: twenty
+  leaves (dqz.h, "the Rainbow agent")."""
+  offs = (_i64 * RAINBOW_NUM_LEAVES)()
+  sizes = (_i64 * RAINBOW_NUM_LEAVES)()
+  total = _i64()
+  check(lib().dqz_rainbow_param_layout(
+      int(num_actions), int(num_atoms), offs, sizes, ctypes.byref(total)))
+  return list(offs), list(sizes), int(total.value)
+
+
+def rainbow_noise_len(num_actions, num_atoms):
+  """Floats of noise one application of the Rainbow network reads."""
+  n = _int()
+  check(lib().dqz_rainbow_noise_len(
+      int(num_actions), int(num_atoms), ctypes.byref(n)))
+  return int(n.value)
 
 
 # dqz_c51_debug_check's and dqz_qr_debug_check's request bits (DQZ_C51_REQ_*)

@@ -137,6 +137,7 @@ DQZ_OTHER_KERNEL __launch_bounds__(256) void c51_logits_kernel(C51LogitsArgs a) 
 // instantiation is the kernel as it was.
 constexpr int WIDE_DOUBLE = 1;    // a* = argmax_a q_values of copy 2, online(s_t), instead of the target's own
 constexpr int WIDE_WEIGHTED = 2;  // loss = mean_b(w_b loss_b): the cotangent times w_b; the priority clip(|loss_b|, 0, 100)
+constexpr int WIDE_NO_DZ1 = 4;   // dz1 is not dl W2^T (the noisy dueling network, rainbow.hpp): W2 is not read, dz1 not written
 constexpr float WIDE_MAX_PRIORITY = 100.f;  // rainbow/agent.py:198
 
 struct C51HeadArgs {
@@ -184,7 +185,7 @@ __device__ __forceinline__ float wave_max(float m) {
 // the register allocation moves).
 template <int MODE>
 DQZ_OTHER_KERNEL __launch_bounds__(512) void c51_head_kernel(C51HeadArgs h) {
-  constexpr bool DQ = MODE & WIDE_DOUBLE, WT = MODE & WIDE_WEIGHTED;
+  constexpr bool DQ = MODE & WIDE_DOUBLE, WT = MODE & WIDE_WEIGHTED, DZ = !(MODE & WIDE_NO_DZ1);
   __shared__ float s_lg[2][C51_MAXOUT];
   __shared__ float s_z[C51_MAXN], s_p[C51_MAXN];
   __shared__ float s_dlp[3 + 16 * ((C51_MAXN + 3 + 15) / 16) + 1];  // dlogits at [3, 3 + N), zeros around them
@@ -213,7 +214,7 @@ DQZ_OTHER_KERNEL __launch_bounds__(512) void c51_head_kernel(C51HeadArgs h) {
     d = rv.z;
     if (WT) wt = h.weights[b];
 #pragma unroll
-    for (int p = 0; p < DZ_P; ++p) {
+    for (int p = 0; DZ && p < DZ_P; ++p) {
       const int row = 128 * p + (n >> 2);
       const int64_t base = (int64_t)row * AN + a_tm1 * N;
       off[p] = (int)(base & 3);
@@ -324,7 +325,7 @@ DQZ_OTHER_KERNEL __launch_bounds__(512) void c51_head_kernel(C51HeadArgs h) {
   __syncthreads();
   // dz1[b][row] = relu'(z1) sum_k dlogits[k] W2[row][a_b N + k]: window float f pairs with dlogits[f - off]
 #pragma unroll
-  for (int p = 0; p < DZ_P; ++p) {
+  for (int p = 0; DZ && p < DZ_P; ++p) {
     float dz = 0.f;
 #pragma unroll
     for (int j = 0; j < DZ_J; ++j)

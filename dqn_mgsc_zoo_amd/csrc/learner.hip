@@ -4,7 +4,8 @@
 // learned-logit and prioritized samplers, sum trees), the MGSC meta-update
 // and its HVP, Atari preprocessing, the optimizers applied to a finished
 // gradient (Adam, plain RMSProp, global-norm clipping), the categorical (C51)
-// and quantile (QR-DQN) heads the learner step launches in place of its own,
+// and quantile (QR-DQN) heads the learner step launches in place of its own, the
+// Rainbow agent's noisy dueling network around the categorical head,
 // and the C-ABI entries that drive them.
 #include <hip/hip_runtime.h>
 
@@ -24,6 +25,7 @@
 #include "optim.hpp"
 #include "c51.hpp"
 #include "qr.hpp"
+#include "rainbow.hpp"
 
 using namespace dqz;
 
@@ -652,18 +654,35 @@ int dqz_learner_step_per_draw(dqz_learner* L, const dqz_params* P, const dqz_sto
 struct dqz_optimizer {
   dqz_optimizer_config cfg;
   int64_t total;
-  OptLeaves lv;
+  OptLeavesRb lv;     // every layout in the widest table: leaves the layout does not have are empty
   int nblocks;        // workgroups of the apply launch
   int nparts;         // workgroups of the norm launch = its partials
   float* grad;        // [total] the steps' gradient; padding zero since creation
   double* part;       // [nparts] sums of squares of the last gradient normed
   const float* last;  // the most recent apply's gradient (dqz_optimizer_outputs without clipping)
   int wide_n;         // 0: dqz_param_layout; N: a wide head's layout (dqz_c51_param_layout, dqz_qr_param_layout)
+  int rb;             // 1: the Rainbow network's twenty leaves (dqz_rainbow_param_layout), wide_n its N
   void* block;
 };
 
+// The Rainbow network's layout (dqz.h, "the Rainbow agent"): leaves 0-7 are any DQN network's, A1-mu being fc1.
+static void rb_param_layout(int A, int N, int64_t off[DQZ_RAINBOW_NUM_LEAVES], int64_t sz[DQZ_RAINBOW_NUM_LEAVES],
+                            int64_t* total) {
+  const int64_t w1 = (int64_t)FLAT * HID, wa = (int64_t)HID * A * N, wv = (int64_t)HID * N;
+  const int64_t sizes[DQZ_RAINBOW_NUM_LEAVES] = {C1KK * C1CO, C1CO, C2KK * C2CO, C2CO, C3KK * C3CO, C3CO,
+                                                 w1, HID, w1, HID, wa, wa, (int64_t)A * N,
+                                                 w1, HID, w1, HID, wv, wv, N};
+  int64_t o = 0;
+  for (int i = 0; i < DQZ_RAINBOW_NUM_LEAVES; ++i) {
+    off[i] = o;
+    sz[i] = sizes[i];
+    o += (sizes[i] + 63) / 64 * 64;
+  }
+  *total = o;
+}
+
 // wide_n = 0: the scalar head's layout; N: a wide head's (fc2 leaves A * N wide, no shared bias)
-static int optimizer_create(const dqz_optimizer_config* cfg, int wide_n, dqz_optimizer** out) {
+static int optimizer_create(const dqz_optimizer_config* cfg, int wide_n, dqz_optimizer** out, int rb = 0) {
   if (!cfg || !out) return fail(DQZ_ERR_INVALID, "null argument");
   if (cfg->kind != DQZ_OPT_ADAM && cfg->kind != DQZ_OPT_RMSPROP)
     return fail(DQZ_ERR_INVALID, "optimizer kind must be DQZ_OPT_ADAM or DQZ_OPT_RMSPROP");
@@ -676,14 +695,18 @@ static int optimizer_create(const dqz_optimizer_config* cfg, int wide_n, dqz_opt
   dqz_optimizer* o = new dqz_optimizer();
   o->cfg = *cfg;
   o->wide_n = wide_n;
-  int64_t off[10], sz[10];
-  if (wide_n)
+  o->rb = rb;
+  int64_t off[DQZ_RAINBOW_NUM_LEAVES], sz[DQZ_RAINBOW_NUM_LEAVES];
+  if (rb)
+    rb_param_layout(cfg->num_actions, wide_n, off, sz, &o->total);
+  else if (wide_n)
     wide_param_layout(cfg->num_actions, wide_n, off, sz, &o->total);
   else
     param_layout(cfg->num_actions, cfg->shared_bias, off, sz, &o->total);
-  for (int i = 0; i < 10; ++i) {
-    o->lv.off4[i] = off[i] / 4;
-    o->lv.end[i] = off[i] + sz[i];
+  const int leaves = rb ? DQZ_RAINBOW_NUM_LEAVES : DQZ_NUM_LEAVES;
+  for (int i = 0; i < DQZ_RAINBOW_NUM_LEAVES; ++i) {  // leaves the layout does not have: empty, behind the last float4
+    o->lv.off4[i] = i < leaves ? off[i] / 4 : o->total / 4;
+    o->lv.end[i] = i < leaves ? off[i] + sz[i] : o->total;
   }
   o->lv.n4 = o->total / 4;
   o->nblocks = (int)((o->lv.n4 + OPT_THREADS * OPT_UNROLL - 1) / (OPT_THREADS * OPT_UNROLL));
@@ -713,8 +736,51 @@ int dqz_optimizer_destroy(dqz_optimizer* o) {
   return DQZ_OK;
 }
 
+// The ten-leaf table of the kernels every layout but the Rainbow network's runs on
+static OptLeaves opt_leaves10(const dqz_optimizer* o) {
+  OptLeaves lv;
+  for (int i = 0; i < DQZ_NUM_LEAVES; ++i) {
+    lv.off4[i] = o->lv.off4[i];
+    lv.end[i] = o->lv.end[i];
+  }
+  lv.n4 = o->lv.n4;
+  return lv;
+}
+
+}  // extern "C"
+
+// An apply kernel's argument on either table
+template <class Args, class Leaves>
+static Args opt_args(const dqz_optimizer* o, const Leaves& lv, float* th, const float* grad, float* mu, float* nu,
+                     int32_t* count, bool clip) {
+  Args a{};
+  a.lv = lv;
+  a.th = (float4*)th;
+  a.m = (float4*)mu;
+  a.v = (float4*)nu;
+  a.g = (const float4*)grad;
+  a.kind = o->cfg.kind;
+  a.lr = o->cfg.learning_rate;
+  a.b1 = o->cfg.b1;
+  a.b2 = o->cfg.b2;
+  a.decay = o->cfg.decay;
+  a.eps = o->cfg.eps;
+  a.clip = o->cfg.max_global_grad_norm;
+  a.part = clip ? o->part : nullptr;
+  a.nparts = o->nparts;
+  a.count = count;
+  return a;
+}
+
+extern "C" {
+
 static int opt_norm(dqz_optimizer* o, const float* grad, hipStream_t st) {
-  hipLaunchKernelGGL(opt_norm_kernel, dim3(o->nparts), dim3(OPT_THREADS), 0, st, (const float4*)grad, o->lv, o->part);
+  if (o->rb)
+    hipLaunchKernelGGL(opt_norm_rb_kernel, dim3(o->nparts), dim3(OPT_THREADS), 0, st, (const float4*)grad, o->lv,
+                       o->part);
+  else
+    hipLaunchKernelGGL(opt_norm_kernel, dim3(o->nparts), dim3(OPT_THREADS), 0, st, (const float4*)grad,
+                       opt_leaves10(o), o->part);
   DQZ_HIP(hipGetLastError());
   return DQZ_OK;
 }
@@ -731,28 +797,23 @@ int dqz_optimizer_apply(dqz_optimizer* o, float* th, const float* grad, float* m
   const bool clip = o->cfg.max_global_grad_norm > 0.f;
   if (clip)
     if (int rc = opt_norm(o, grad, st)) return rc;
-  OptArgs a{};
-  a.th = (float4*)th;
-  a.m = (float4*)mu;
-  a.v = (float4*)nu;
-  a.g = (const float4*)grad;
-  a.lv = o->lv;
-  a.kind = o->cfg.kind;
-  a.lr = o->cfg.learning_rate;
-  a.b1 = o->cfg.b1;
-  a.b2 = o->cfg.b2;
-  a.decay = o->cfg.decay;
-  a.eps = o->cfg.eps;
-  a.clip = o->cfg.max_global_grad_norm;
-  a.part = clip ? o->part : nullptr;
-  a.nparts = o->nparts;
-  a.count = count;
+  const dim3 grid(o->nblocks), block(OPT_THREADS);
+  if (o->rb) {
+    const OptArgsRb a = opt_args<OptArgsRb>(o, o->lv, th, grad, mu, nu, count, clip);
+    if (is_adam)
+      hipLaunchKernelGGL(opt_adam_rb_kernel, grid, block, 0, st, a);
+    else
+      hipLaunchKernelGGL(opt_rms_rb_kernel, grid, block, 0, st, a);
+  } else {
+    const OptArgs a = opt_args<OptArgs>(o, opt_leaves10(o), th, grad, mu, nu, count, clip);
+    if (is_adam)
+      hipLaunchKernelGGL(opt_adam_kernel, grid, block, 0, st, a);
+    else
+      hipLaunchKernelGGL(opt_rms_kernel, grid, block, 0, st, a);
+  }
   if (is_adam) {
-    hipLaunchKernelGGL(opt_adam_kernel, dim3(o->nblocks), dim3(OPT_THREADS), 0, st, a);
     DQZ_HIP(hipGetLastError());
     hipLaunchKernelGGL(opt_count_kernel, dim3(1), dim3(64), 0, st, count);
-  } else {
-    hipLaunchKernelGGL(opt_rms_kernel, dim3(o->nblocks), dim3(OPT_THREADS), 0, st, a);
   }
   DQZ_HIP(hipGetLastError());
   o->last = grad;
@@ -783,7 +844,7 @@ static int check_step_apply(const dqz_learner* L, const dqz_params* P, const dqz
        reinterpret_cast<uintptr_t>(P->mu)) % 16)
     return fail(DQZ_ERR_INVALID, "parameters and moments must be 16-byte aligned");
   if (!L || o->cfg.num_actions != L->cfg.num_actions || (o->cfg.shared_bias != 0) != (L->shared_bias != 0) ||
-      o->wide_n != (wide ? wide->N : 0))
+      o->wide_n != (wide ? wide->N : 0) || o->rb != (wide && wide->kind == WIDE_RB ? 1 : 0))
     return fail(DQZ_ERR_INVALID, "the optimizer was created for another parameter layout");
   return DQZ_OK;
 }
@@ -939,6 +1000,8 @@ static QrHeadArgs qr_head_args(const WideHead& c, int Z, int B, int A) {
   return h;
 }
 
+static int rb_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, hipStream_t st);
+
 int dqz::wide_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const WideHead& c = *r.wide;
@@ -946,6 +1009,7 @@ int dqz::wide_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, cons
   const int B = L->cfg.batch, A = L->cfg.num_actions, N = c.N;
   const int Z = L->Z;  // 3 with double_q: the selector, online(s_t), is copy 2
   const int mode = (c.double_q ? WIDE_DOUBLE : 0) | (c.weighted ? WIDE_WEIGHTED : 0);
+  if (c.kind == WIDE_RB) return rb_launch(which, L, P, r, st);
   if (which == WIDE_OUTPUTS) {
     const NetZ nz{{P->online, P->target, P->online}, {0, 1, 1}};
     return c51_logits(L, nz, Z, B, A * N, c.out, st);
@@ -1474,6 +1538,348 @@ int dqz_qr_debug_check(int batch, unsigned request) { return wide_debug_check(WI
 int dqz_qr_debug_check_opt(int batch, unsigned request, const dqz_wide_options* options) {
   if (int rc = wide_check_options(options)) return rc;
   return wide_debug_check(WIDE_QR, batch, request, options);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// the Rainbow agent (rainbow.hpp): a categorical head (double_q and weighted) behind the noisy dueling network
+
+// The wide handle plus what the noisy layers need.  Of the inner learner's buffers fc1p holds A1-mu's partials,
+// h1 is h_adv, dz1 is dz_adv and dy3 the combined dX, so the step's own fc1 dW and update find A1-mu as fc1.
+struct dqz_rainbow {
+  dqz_wide* W;
+  RbLeaves lf;
+  RbNoise nl;
+  int64_t off[DQZ_RAINBOW_NUM_LEAVES], sz[DQZ_RAINBOW_NUM_LEAVES], total;
+  const float* noise;  // the running call's: [3][len] of a step, [len] of a forward
+  float* ys;           // [2][Z][B][3136] e_in * y3 of A1 and of V1
+  float* part[3];      // [Z][S][B][512] split-K partials of V1-mu, A1-sigma, V1-sigma
+  float *h_val, *adv, *val;              // [Z][B][512], [Z][B][A N], [Z][B][N]
+  float *dz_val, *dz_adv_e, *dz_val_e;   // [B][512]
+  float* dx;                             // [4][B][3136]
+  void* block;
+};
+
+// Everything between the torso's fc1 launch (A1-mu, in L->fc1p) and the head: q_logits of Z applications on B
+// rows into the head's `out`.
+static int rb_outputs(dqz_rainbow* R, const NetZ& nz, int Z, int B, hipStream_t st) {
+  dqz_learner* L = R->W->L;
+  const int A = R->W->A, N = R->W->N, AN = A * N;
+  const int64_t rows = (int64_t)Z * B;
+  RbScaleArgs sc{L->y3, R->noise, R->nl, Z, B, R->ys};
+  hipLaunchKernelGGL(rb_scale_kernel, dim3((unsigned)((rows * (FLAT / 4) + 255) / 256)), dim3(256), 0, st, sc);
+  DQZ_HIP(hipGetLastError());
+  Fc1FwdArgs f = make_fwd_args(L, nz, Z, B, Conv1Src{}).f1;
+  const struct {
+    const float* in;
+    int64_t w_off;
+  } prod[3] = {{L->y3, R->lf.v1w}, {R->ys, R->lf.a1sw}, {R->ys + rows * FLAT, R->lf.v1sw}};
+  for (int i = 0; i < 3; ++i) {
+    f.in = prod[i].in;
+    f.w_off = prod[i].w_off;
+    f.part = R->part[i];
+    if (int rc = fc1_forward(f, Z, st)) return rc;
+  }
+  RbHiddenArgs h{};
+  h.part[0] = L->fc1p;
+  h.part[1] = R->part[0];
+  h.part[2] = R->part[1];
+  h.part[3] = R->part[2];
+  h.S = L->S_fc1;
+  h.nz = nz;
+  h.lf = R->lf;
+  h.noise = R->noise;
+  h.nl = R->nl;
+  h.Z = Z;
+  h.B = B;
+  h.h_adv = L->h1;
+  h.h_val = R->h_val;
+  hipLaunchKernelGGL(rb_hidden_kernel, dim3((unsigned)((rows * HID + 255) / 256)), dim3(256), 0, st, h);
+  DQZ_HIP(hipGetLastError());
+  RbLogitsArgs g{L->h1, R->h_val, nz, R->lf, R->noise, R->nl, Z, B, AN, N, R->adv, R->val};
+  hipLaunchKernelGGL(rb_logits_kernel, dim3((AN + N + 255) / 256, (unsigned)rows), dim3(256), 0, st, g);
+  DQZ_HIP(hipGetLastError());
+  RbCombineArgs c{R->adv, R->val, Z, B, A, N, R->W->head.out};
+  hipLaunchKernelGGL(rb_combine_kernel, dim3((unsigned)((rows * N + 255) / 256)), dim3(256), 0, st, c);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+static int rb_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, hipStream_t st) {
+  const WideHead& c = *r.wide;
+  dqz_rainbow* R = static_cast<dqz_rainbow*>(c.rb);
+  const int B = L->cfg.batch, A = L->cfg.num_actions, N = c.N;
+  if (which == WIDE_OUTPUTS) {
+    const NetZ nz{{P->online, P->target, P->online}, {0, 1, 1}};
+    return rb_outputs(R, nz, L->Z, B, st);
+  }
+  if (which == WIDE_HEAD) {
+    C51HeadArgs h = c51_head_args(c, L->Z, B, A);
+    h.rec = reinterpret_cast<const float4*>(L->rec);
+    h.qv = c.qv;
+    h.la = c.taken;
+    h.dl = c.dtaken;
+    h.astar = c.astar;
+    h.loss_part = L->loss_part;
+    h.gq = L->gq;
+    h.ga = L->ga;
+    h.weights = r.is_weights;
+    h.loss_b = c.loss_b;
+    h.prio = L->td;
+    hipLaunchKernelGGL(c51_head_kernel<WIDE_DOUBLE | WIDE_WEIGHTED | WIDE_NO_DZ1>, dim3(B), dim3(HID), 0, st, h);
+  } else if (which == WIDE_DZ1) {
+    RbDhiddenArgs d{c.dtaken, L->ga, L->h1, R->h_val, P->online, R->lf, R->noise, R->nl, B, A, N,
+                    L->dz1, R->dz_val, R->dz_adv_e, R->dz_val_e};
+    hipLaunchKernelGGL(rb_dhidden_kernel, dim3(B, HID / RB_DH_ROWS), dim3(512), 0, st, d);
+  } else if (which == WIDE_FC1_DX) {
+    const int64_t n = (int64_t)B * FLAT;
+    Fc1BwdArgs f{};
+    f.y3 = L->y3;
+    f.th = P->online;
+    f.B = B;
+    const struct {
+      const float* dz;
+      int64_t w_off;
+    } prod[4] = {{L->dz1, R->lf.a1w}, {R->dz_val, R->lf.v1w}, {R->dz_adv_e, R->lf.a1sw}, {R->dz_val_e, R->lf.v1sw}};
+    for (int i = 0; i < 4; ++i) {
+      f.dz1 = prod[i].dz;
+      f.w_off = prod[i].w_off;
+      f.dy3 = R->dx + i * n;
+      // the dX-ordered W3 / W2 copies of this step: written by the first launch alone
+      f.w3 = i == 0 ? P->online + L->off[4] : nullptr;
+      f.w2 = i == 0 ? P->online + L->off[2] : nullptr;
+      f.w3p = i == 0 ? L->w3p : nullptr;
+      f.w2p = i == 0 ? L->w2p : nullptr;
+      if (int rc = fc1_dx(f, st)) return rc;
+    }
+    RbDxCombineArgs x{R->dx, R->noise, R->nl, B, L->dy3};
+    hipLaunchKernelGGL(rb_dx_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x);
+  } else {  // WIDE_FC2_GRAD: every fc leaf but A1-mu
+    RbFc2GradArgs g{c.dtaken, L->ga, L->h1, R->h_val, R->dz_val, R->dz_adv_e, R->dz_val_e, R->noise, R->nl, R->lf,
+                    B, A, N, r.gout, r.gacc};
+    hipLaunchKernelGGL(rb_fc2_grad_kernel, dim3((unsigned)((rb_fc2_grad_elems(A * N, N) + 255) / 256)), dim3(256), 0,
+                       st, g);
+    DQZ_HIP(hipGetLastError());
+    RbFc1DwArgs w{{L->y3, R->ys, R->ys + (int64_t)L->Z * B * FLAT}, {R->dz_val, R->dz_adv_e, R->dz_val_e},
+                  {R->lf.v1w, R->lf.a1sw, R->lf.v1sw}, B, r.gout, r.gacc};
+    hipLaunchKernelGGL(rb_fc1_dw_kernel, dim3(FLAT * (HID / 4) / 256, 3), dim3(256), 0, st, w);
+  }
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+static dqz_wide* wide_of(dqz_rainbow* R) { return R ? R->W : nullptr; }
+
+// q_values of n states through one application of the network under `noise`
+static int rb_forward_q(dqz_rainbow* R, const float* params, const Conv1Src& src, int which, int n,
+                        const float* noise, float* q_out, hipStream_t st) {
+  dqz_wide* W = R->W;
+  if (reinterpret_cast<uintptr_t>(params) % 16) return fail(DQZ_ERR_INVALID, "parameters must be 16-byte aligned");
+  if (int rc = forward_torso(W->L, params, src, which, n, st)) return rc;
+  R->noise = noise;
+  const NetZ nz{{params, params, params}, {which, which, which}};
+  if (int rc = rb_outputs(R, nz, 1, n, st)) return rc;
+  C51HeadArgs h = c51_head_args(W->head, 1, n, W->A);
+  set_forward(&h, q_out, nullptr);
+  hipLaunchKernelGGL(c51_head_kernel<0>, dim3(n), dim3(HID), 0, st, h);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+static int rb_check_step(const dqz_rainbow* R, const float* is_weights, const float* noise) {
+  if (!R || !is_weights || !noise) return fail(DQZ_ERR_INVALID, "null argument");
+  return DQZ_OK;
+}
+
+extern "C" {
+
+int dqz_rainbow_param_layout(int num_actions, int num_atoms, int64_t offsets[DQZ_RAINBOW_NUM_LEAVES],
+                             int64_t sizes[DQZ_RAINBOW_NUM_LEAVES], int64_t* total) {
+  if (int rc = wide_check_shape(WIDE_RB, num_actions, num_atoms)) return rc;
+  if (!offsets || !sizes || !total) return fail(DQZ_ERR_INVALID, "null output pointer");
+  rb_param_layout(num_actions, num_atoms, offsets, sizes, total);
+  return DQZ_OK;
+}
+
+int dqz_rainbow_noise_len(int num_actions, int num_atoms, int* out) {
+  if (int rc = wide_check_shape(WIDE_RB, num_actions, num_atoms)) return rc;
+  if (!out) return fail(DQZ_ERR_INVALID, "null output pointer");
+  *out = rb_noise_layout(num_actions, num_atoms).len;
+  return DQZ_OK;
+}
+
+int dqz_rainbow_noise(uint64_t seed, uint64_t* counter_dev, int n, float* out, void* stream) {
+  if (!counter_dev || !out || n < 1 || n > 65536) return fail(DQZ_ERR_INVALID, "bad argument");
+  hipLaunchKernelGGL(rb_noise_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, seed, counter_dev, n,
+                     out);
+  DQZ_HIP(hipGetLastError());
+  hipLaunchKernelGGL(rb_noise_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, counter_dev, n);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+int dqz_rainbow_optimizer_create(const dqz_optimizer_config* cfg, int num_atoms, dqz_optimizer** out) {
+  if (!cfg || !out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (int rc = wide_check_shape(WIDE_RB, cfg->num_actions, num_atoms)) return rc;
+  if (cfg->shared_bias) return fail(DQZ_ERR_INVALID, "the %s head has no shared bias", kWide[WIDE_RB].noun);
+  return optimizer_create(cfg, num_atoms, out, 1);
+}
+
+int dqz_rainbow_create(const dqz_learner_config* cfg, int num_atoms, const float* support,
+                       const dqz_wide_options* options, dqz_rainbow** out) {
+  if (!cfg || !support || !out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (options && (options->double_q != 1 || options->weighted != 1))
+    return fail(DQZ_ERR_INVALID, "the rainbow step is always double-Q and weighted: options must be {1, 1} or null");
+  if (int rc = wide_check_config(WIDE_RB, cfg, num_atoms)) return rc;
+  float z[C51_MAXN];
+  DQZ_HIP(hipMemcpy(z, support, sizeof(float) * num_atoms, hipMemcpyDefault));
+  for (int i = 0; i < num_atoms; ++i)
+    if (!std::isfinite(z[i]) || (i > 0 && !(z[i] > z[i - 1])))
+      return fail(DQZ_ERR_INVALID, "support must be finite and strictly increasing (atom %d)", i);
+  const dqz_wide_options both{1, 1};
+  dqz_wide* W = nullptr;
+  if (int rc = wide_create(WIDE_RB, cfg, num_atoms, z, 0.f, &both, &W)) return rc;
+  dqz_rainbow* R = new dqz_rainbow();
+  R->W = W;
+  W->head.rb = R;
+  dqz_learner* L = W->L;
+  const int A = cfg->num_actions, N = num_atoms;
+  rb_param_layout(A, N, R->off, R->sz, &R->total);
+  for (int i = 0; i < 10; ++i) {  // the step's view: leaves 0-7 (A1-mu as fc1); 8 and 9 it never touches behind a wide head
+    L->off[i] = R->off[i];
+    L->sz[i] = R->sz[i];
+  }
+  L->total = R->total;
+  const int64_t* o = R->off;
+  R->lf = RbLeaves{o[6], o[7], o[8], o[9], o[10], o[11], o[12], o[13], o[14], o[15], o[16], o[17], o[18], o[19]};
+  R->nl = rb_noise_layout(A, N);
+  const auto pad = [](int64_t n) { return (n + 63) / 64 * 64; };
+  const int64_t B = cfg->batch, Z = L->Z, AN = (int64_t)A * N;
+  const int64_t n_ys = pad(2 * Z * B * FLAT), n_part = pad(Z * L->S_fc1 * B * HID), n_h = pad(Z * B * HID);
+  const int64_t n_adv = pad(Z * B * AN), n_val = pad(Z * B * N), n_dz = pad(B * HID), n_dx = pad(4 * B * FLAT);
+  const int64_t floats = n_ys + 3 * n_part + n_h + n_adv + n_val + 3 * n_dz + n_dx;
+  if (hipMalloc(&R->block, floats * sizeof(float)) != hipSuccess ||
+      hipMemset(R->block, 0, floats * sizeof(float)) != hipSuccess) {
+    if (R->block) (void)hipFree(R->block);
+    (void)wide_destroy(W);
+    delete R;
+    return fail(DQZ_ERR_HIP, "hipMalloc of %lld bytes of rainbow scratch failed", (long long)(floats * 4));
+  }
+  float* p = (float*)R->block;
+  R->ys = p;
+  p += n_ys;
+  for (int i = 0; i < 3; ++i, p += n_part) R->part[i] = p;
+  R->h_val = p;
+  p += n_h;
+  R->adv = p;
+  p += n_adv;
+  R->val = p;
+  p += n_val;
+  R->dz_val = p;
+  R->dz_adv_e = p + n_dz;
+  R->dz_val_e = p + 2 * n_dz;
+  p += 3 * n_dz;
+  R->dx = p;
+  *out = R;
+  return DQZ_OK;
+}
+
+int dqz_rainbow_destroy(dqz_rainbow* R) {
+  if (!R) return DQZ_OK;
+  if (R->block) (void)hipFree(R->block);
+  (void)wide_destroy(R->W);
+  delete R;
+  return DQZ_OK;
+}
+
+int dqz_rainbow_learner(dqz_rainbow* R, dqz_learner** out) { return wide_learner(wide_of(R), out); }
+
+int dqz_rainbow_step(dqz_rainbow* R, const dqz_params* P, const dqz_store* S, const int32_t* slots,
+                     const float* is_weights, const float* noise, dqz_optimizer* o, int32_t* count, void* stream) {
+  if (int rc = rb_check_step(R, is_weights, noise)) return rc;
+  R->noise = noise;
+  return wide_step(R->W, P, S, slots, is_weights, o, count, stream);
+}
+
+int dqz_rainbow_grad(dqz_rainbow* R, const dqz_params* P, const dqz_store* S, const int32_t* slots,
+                     const float* is_weights, const float* noise, float* grad_out, void* stream) {
+  if (int rc = rb_check_step(R, is_weights, noise)) return rc;
+  R->noise = noise;
+  return wide_grad(R->W, P, S, slots, is_weights, grad_out, stream);
+}
+
+int dqz_rainbow_profile(dqz_rainbow* R, const dqz_params* P, const dqz_store* S, const int32_t* slots,
+                        const float* is_weights, const float* noise, float* grad_out, int iters, float* phase_ms,
+                        void* stream) {
+  if (int rc = rb_check_step(R, is_weights, noise)) return rc;
+  R->noise = noise;
+  return wide_profile(R->W, P, S, slots, is_weights, grad_out, iters, phase_ms, stream);
+}
+
+int dqz_rainbow_outputs(dqz_rainbow* R, float* logits_a, float* q_values, float* loss_b, float* loss,
+                        int32_t* a_star, void* stream) {
+  return wide_outputs(wide_of(R), logits_a, q_values, loss_b, loss, a_star, stream);
+}
+
+int dqz_rainbow_outputs_opt(dqz_rainbow* R, float* q_selector, float* priorities, void* stream) {
+  return wide_outputs_opt(wide_of(R), q_selector, priorities, stream);
+}
+
+int dqz_rainbow_debug_head(dqz_rainbow* R, float* q_logits, float* dlogits, void* stream) {
+  return wide_debug(wide_of(R), q_logits, dlogits, stream);
+}
+
+int dqz_rainbow_debug(dqz_rainbow* R, float* h_adv, float* h_val, float* adv, float* val, float* dz_adv,
+                      float* dz_val, void* stream) {
+  if (!R) return fail(DQZ_ERR_INVALID, "null argument");
+  hipStream_t st = (hipStream_t)stream;
+  const dqz_learner* L = R->W->L;
+  const int64_t B = L->cfg.batch, AN = (int64_t)R->W->A * R->W->N;
+  const struct {
+    float* dst;
+    const float* src;
+    int64_t n;
+  } rows[] = {{h_adv, L->h1, B * HID},    {h_val, R->h_val, B * HID},  {adv, R->adv, B * AN},
+              {val, R->val, B * R->W->N}, {dz_adv, L->dz1, B * HID},   {dz_val, R->dz_val, B * HID}};
+  for (const auto& r : rows)
+    if (r.dst) DQZ_HIP(hipMemcpyAsync(r.dst, r.src, 4 * r.n, hipMemcpyDeviceToDevice, st));
+  return DQZ_OK;
+}
+
+int dqz_rainbow_forward(dqz_rainbow* R, const float* params, const uint8_t* states, int n, const float* noise,
+                        float* q_out, void* stream) {
+  if (!R || !noise) return fail(DQZ_ERR_INVALID, "null argument");
+  Conv1Src src;
+  if (int rc = forward_src(R->W->L, params, n, {.states = states, .q_out = q_out}, &src)) return rc;
+  return rb_forward_q(R, params, src, 0, n, noise, q_out, (hipStream_t)stream);
+}
+
+int dqz_rainbow_forward_slots(dqz_rainbow* R, const float* params, const dqz_store* S, const int32_t* slots, int n,
+                              int which, const float* noise, float* q_out, void* stream) {
+  if (!R || !noise) return fail(DQZ_ERR_INVALID, "null argument");
+  Conv1Src src;
+  const ForwardInput in{.from_store = true, .store = S, .slots = slots, .which = which, .q_out = q_out};
+  if (int rc = forward_src(R->W->L, params, n, in, &src)) return rc;
+  return rb_forward_q(R, params, src, which, n, noise, q_out, (hipStream_t)stream);
+}
+
+int dqz_rainbow_act(dqz_rainbow* R, const float* params, const uint8_t* states, int n, const float* noise,
+                    dqz_action* out, void* stream) {
+  if (!R || !noise) return fail(DQZ_ERR_INVALID, "null argument");
+  ActorDraw act{0.0, 0, 0, out};  // no epsilon: forward_src's checks and device views of states and out
+  Conv1Src src;
+  if (int rc = forward_src(R->W->L, params, n, {.states = states, .act = &act}, &src)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = rb_forward_q(R, params, src, 0, n, noise, R->W->head.qv, st)) return rc;
+  hipLaunchKernelGGL(rb_act_kernel, dim3((n + 63) / 64), dim3(64), 0, st, R->W->head.qv, n, R->W->A, act.out);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+int dqz_rainbow_debug_check(int batch, unsigned request) {
+  const dqz_wide_options both{1, 1};
+  return wide_debug_check(WIDE_RB, batch, request, &both);
 }
 
 }  // extern "C"

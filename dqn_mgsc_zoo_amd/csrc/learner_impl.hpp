@@ -233,7 +233,11 @@ struct MetaSoftmax {
 // (QR-DQN; qr.hpp) one.  The learner's parameter layout then ends in fc2 leaves A * N wide (wide_param_layout;
 // the quantile head's columns are quantile-major, i A + a), the step runs in gradient mode, and the head's and
 // the fc2 gradient's launches, which live in the other code object, are made by wide_launch.
-enum WideKind { WIDE_C51, WIDE_QR };
+// WIDE_RB is the categorical head behind the noisy dueling network of the Rainbow agent (rainbow.hpp): its loss,
+// projection, a* and priorities are the categorical head's with double_q and weighted both set, and the launches
+// around it (the other three fc1 products, both noisy fc2 layers, the dueling combine and their backward) are
+// wide_launch's as well.
+enum WideKind { WIDE_C51, WIDE_QR, WIDE_RB };
 struct WideHead {
   WideKind kind;
   int N;              // atoms / quantiles per action
@@ -252,6 +256,7 @@ struct WideHead {
   int weighted;       // every step takes is_weights [B]; the head writes clip(|loss_b|, 0, 100) to the learner's td
   float* loss_b;      // [B] the unweighted per-sample loss of a weighted head (the learner's loss_part then holds
                       // w_b loss_b, what the update sums); null otherwise
+  void* rb;           // WIDE_RB alone: the dqz_rainbow that owns this head (learner.hip)
 };
 constexpr int C51_MAX_ATOMS = 64, C51_MAX_OUT = 1024;     // c51.hpp's C51_MAXN / C51_MAXOUT
 constexpr int QR_MAX_QUANTILES = 256, QR_MAX_OUT = 4096;  // qr.hpp's QR_MAXN / QR_MAXOUT
@@ -263,7 +268,7 @@ struct WideDesc {
   int min_n, max_n, max_out;
   const char *no_meta, *no_unit, *no_wb, *no_fused;
 };
-inline constexpr WideDesc kWide[2] = {
+inline constexpr WideDesc kWide[3] = {
     {"categorical", "num_atoms", "support", 2, C51_MAX_ATOMS, C51_MAX_OUT,
      "the categorical head has no MGSC meta mode", "the categorical head has no unit-cotangent pass",
      "the categorical head has no TD error to write back as a priority",
@@ -271,12 +276,16 @@ inline constexpr WideDesc kWide[2] = {
     {"quantile", "num_quantiles", "quantiles", 1, QR_MAX_QUANTILES, QR_MAX_OUT,
      "the quantile head takes no MGSC meta mode", "the quantile head takes no unit-cotangent pass",
      "the quantile head takes no PER priority write-back",
-     "the quantile head takes no fused centered RMSProp (it runs in gradient mode only)"}};
+     "the quantile head takes no fused centered RMSProp (it runs in gradient mode only)"},
+    {"rainbow", "num_atoms", "support", 2, C51_MAX_ATOMS, C51_MAX_OUT,
+     "the rainbow head has no MGSC meta mode", "the rainbow head has no unit-cotangent pass",
+     "the rainbow head writes its priorities back through dqz_per_write_back (no fused write-back)",
+     "the rainbow head runs in gradient mode only (no fused centered RMSProp)"}};
 
 inline void wide_param_layout(int A, int N, int64_t off[10], int64_t sz[10], int64_t* total) {
   param_layout(A * N, 0, off, sz, total);  // leaves 0-7 are any DQN network's; fc2 is [512, A N] + [A N]
 }
-enum WideLaunch { WIDE_OUTPUTS, WIDE_HEAD, WIDE_DZ1, WIDE_FC2_GRAD };
+enum WideLaunch { WIDE_OUTPUTS, WIDE_HEAD, WIDE_DZ1, WIDE_FC2_GRAD, WIDE_FC1_DX };
 
 // What one learner step is asked to do, set by name ({.slots = ..., .gout = ...}).  Everything left out is the
 // plain step: centered RMSProp on P->online / mu / nu over the batch `slots`.
@@ -308,8 +317,16 @@ struct StepRequest {
 // One of a wide head's launches of a learner step (learner.hip): the outputs of both copies (c51_logits_kernel,
 // generic in the output width), the per-sample loss head (batch record from L->rec; the quantile one writes the
 // dense cotangent), the quantile head's dz1 as a batched product (only with WideHead::dout), the fc2 gradient
-// into gout's fc2 leaves.
+// into gout's fc2 leaves.  WIDE_RB: the outputs are the noisy dueling network's q_logits, WIDE_DZ1 forms both
+// streams' dz, WIDE_FC1_DX stands in for the step's fc1 dX launch (four products into dy3), and WIDE_FC2_GRAD
+// writes every fc leaf but A1-mu, which sits where fc1 does and is the step's own.
 int wide_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, void* stream);
+
+// The step's fc1 kernels with other arguments, for a head of the other code object (WIDE_RB: the noisy layers'
+// other three 3136 x 512 products): the split-K forward of Z copies (the kernel forward_impl would choose for
+// f.B) and fc1 dX of f.B samples.
+int fc1_forward(const Fc1FwdArgs& f, int Z, void* stream);
+int fc1_dx(const Fc1BwdArgs& f, void* stream);
 
 // conv1 .. fc1 forward of one network copy on n states (learner_step.hip's forward_impl, Z = 1): the fc1 split-K
 // partials are left in L->fc1p for a head of the other code object.

@@ -14,7 +14,10 @@
 //   7 reduce of every cross-sample / split-K gradient + centered RMSProp
 // With StepRequest::wide the launches of the categorical or the quantile head
 // (c51.hpp, qr.hpp, the other code object; wide_launch) stand in for 4, and the
-// fc2 gradient follows 7 in one of its own.
+// fc2 gradient follows 7 in one of its own.  The Rainbow network (rainbow.hpp)
+// also stands in for 5: its dy3 is the sum of four fc1 dX products, which it
+// launches through fc1_dx below, as it launches its other three fc1 forwards
+// through fc1_forward.
 // What a step is asked to do (batch source, gradient mode, PER write-back,
 // MGSC meta mode, a wide head, profiling) is a StepRequest
 // (learner_impl.hpp), whose fields carry the modes' documentation; the
@@ -314,9 +317,13 @@ int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, c
     // scalar head
     DQZ_PHASE(4, if (int rc = wide_launch(WIDE_OUTPUTS, L, P, r, st)) return rc);
     DQZ_PHASE(8, if (int rc = wide_launch(WIDE_HEAD, L, P, r, st)) return rc);
-    if (r.wide->dout) DQZ_PHASE(2, if (int rc = wide_launch(WIDE_DZ1, L, P, r, st)) return rc);
-    DQZ_PHASE(5, hipLaunchKernelGGL(fc1_dx_kernel, dim3(fc1_dx_blocks(B)), dim3(256), 0, st, fb);
-              DQZ_HIP(hipGetLastError()));
+    const bool rb = r.wide->kind == WIDE_RB;
+    if (r.wide->dout || rb) DQZ_PHASE(2, if (int rc = wide_launch(WIDE_DZ1, L, P, r, st)) return rc);
+    if (rb)  // dy3 is the sum of four products (the noisy layers' mu and sigma of both streams)
+      DQZ_PHASE(5, if (int rc = wide_launch(WIDE_FC1_DX, L, P, r, st)) return rc);
+    else
+      DQZ_PHASE(5, hipLaunchKernelGGL(fc1_dx_kernel, dim3(fc1_dx_blocks(B)), dim3(256), 0, st, fb);
+                DQZ_HIP(hipGetLastError()));
   } else if (B == 1 && !pe.on()) {
     // one sample (the MGSC pass at theta', the HVP's unit-cotangent pass):
     // the head and fc1 dX in one launch, every block forming the head itself
@@ -403,6 +410,22 @@ int dqz::step_enqueue(dqz_learner* L, const dqz_params* P, const dqz_store* S, c
   DQZ_PHASE(9, hipLaunchKernelGGL(update_kernel, dim3(nblk), dim3(256), 0, st, u);
             DQZ_HIP(hipGetLastError()));
   if (wide) DQZ_PHASE(7, if (int rc = wide_launch(WIDE_FC2_GRAD, L, P, r, st)) return rc);
+  return DQZ_OK;
+}
+
+int dqz::fc1_forward(const Fc1FwdArgs& f, int Z, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (f.B <= FC1_GEMV_MAXB)
+    hipLaunchKernelGGL(fc1_gemv_kernel, dim3(fc1_fwd_blocks(Z, 1)), dim3(256), 0, st, f);
+  else
+    hipLaunchKernelGGL(fc1_fwd32_kernel, dim3(fc1_fwd_blocks(Z, f.MG)), dim3(256), 0, st, f);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
+}
+
+int dqz::fc1_dx(const Fc1BwdArgs& f, void* stream) {
+  hipLaunchKernelGGL(fc1_dx_kernel, dim3(fc1_dx_blocks(f.B)), dim3(256), 0, (hipStream_t)stream, f);
+  DQZ_HIP(hipGetLastError());
   return DQZ_OK;
 }
 

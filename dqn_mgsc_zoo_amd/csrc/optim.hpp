@@ -6,7 +6,7 @@
 // step's own kernels (Rms::step); these kernels live in the other code object
 // and run after a learner step in gradient-output mode.
 //
-//   opt_norm_kernel   sum g^2 over the ten leaves (padding excluded) as one
+//   opt_norm_kernel   sum g^2 over the leaves (padding excluded) as one
 //                     float64 partial per workgroup.  Whoever needs the norm
 //                     (the apply, dqz_optimizer_outputs) folds the partials
 //                     itself in index order (opt_fold_norm): no float atomics,
@@ -32,17 +32,23 @@ constexpr int OPT_THREADS = 256;
 constexpr int OPT_UNROLL = 2;  // float4s per thread and array, loaded before the first use
 
 // The parameter layout in float4 units: leaf k holds floats [4 off4[k], end[k]),
-// its padding runs to the next leaf's start (a multiple of 16 float4s).
-struct OptLeaves {
-  int64_t off4[DQZ_NUM_LEAVES], end[DQZ_NUM_LEAVES];
+// its padding runs to the next leaf's start (a multiple of 16 float4s).  NL
+// leaves: ten for the DQN and the wide heads' networks (the kernels below, which
+// are what they were), twenty for the Rainbow network (their _rb twins).
+template <int NL>
+struct OptLeavesT {
+  int64_t off4[NL], end[NL];
   int64_t n4;  // total / 4
 };
+using OptLeaves = OptLeavesT<DQZ_NUM_LEAVES>;
+using OptLeavesRb = OptLeavesT<DQZ_RAINBOW_NUM_LEAVES>;
 
 // real (non-padding) floats of float4 i: 0..4
-__device__ __forceinline__ int opt_real(const OptLeaves& lv, int64_t i) {
+template <int NL>
+__device__ __forceinline__ int opt_real(const OptLeavesT<NL>& lv, int64_t i) {
   int64_t end = lv.end[0];
 #pragma unroll
-  for (int k = 1; k < DQZ_NUM_LEAVES; ++k) end = i >= lv.off4[k] ? lv.end[k] : end;
+  for (int k = 1; k < NL; ++k) end = i >= lv.off4[k] ? lv.end[k] : end;
   const int64_t r = end - 4 * i;
   return r < 0 ? 0 : r > 4 ? 4 : (int)r;
 }
@@ -50,8 +56,9 @@ __device__ __forceinline__ int opt_real(const OptLeaves& lv, int64_t i) {
 constexpr int OPT_NORM_UNROLL = 4;  // float4s per thread of the norm pass
 
 // part[blockIdx.x] = sum of g^2 over this workgroup's float4s, padding excluded
-DQZ_OTHER_KERNEL __launch_bounds__(OPT_THREADS) void opt_norm_kernel(const float4* __restrict__ g, OptLeaves lv,
-                                                                double* __restrict__ part) {
+template <int NL>
+__device__ __forceinline__ void opt_norm_body(const float4* __restrict__ g, const OptLeavesT<NL>& lv,
+                                              double* __restrict__ part) {
   __shared__ double sbuf[OPT_THREADS / 64];
   const int64_t i0 = (int64_t)blockIdx.x * (OPT_THREADS * OPT_NORM_UNROLL) + threadIdx.x;
   float4 v[OPT_NORM_UNROLL];
@@ -74,6 +81,14 @@ DQZ_OTHER_KERNEL __launch_bounds__(OPT_THREADS) void opt_norm_kernel(const float
   acc = block_sum_f64(acc, sbuf);
   if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
+DQZ_OTHER_KERNEL __launch_bounds__(OPT_THREADS) void opt_norm_kernel(const float4* __restrict__ g, OptLeaves lv,
+                                                                double* __restrict__ part) {
+  opt_norm_body(g, lv, part);
+}
+DQZ_OTHER_KERNEL __launch_bounds__(OPT_THREADS) void opt_norm_rb_kernel(const float4* __restrict__ g, OptLeavesRb lv,
+                                                                   double* __restrict__ part) {
+  opt_norm_body(g, lv, part);
+}
 
 // sqrt of the partials' sum, the same bits in every workgroup that forms it:
 // thread t adds parts t, t + 256, ... in order, then block_sum_f64's fixed tree.
@@ -83,12 +98,13 @@ __device__ __forceinline__ double opt_fold_norm(const double* __restrict__ part,
   return sqrt(block_sum_f64(s, sbuf));
 }
 
-struct OptArgs {
+template <int NL>
+struct OptArgsT {
   float4* th;
   float4* m;  // Adam's first moment (RMSProp: unused)
   float4* v;  // Adam's second moment / RMSProp's nu
   const float4* g;
-  OptLeaves lv;
+  OptLeavesT<NL> lv;
   int kind;             // DQZ_OPT_*
   double lr, b1, b2, decay, eps;  // the config's floats, widened
   double clip;          // max_global_grad_norm (used when part != null)
@@ -96,6 +112,8 @@ struct OptArgs {
   int nparts;
   const int32_t* count; // Adam's count (device), advanced by opt_count_kernel behind this launch
 };
+using OptArgs = OptArgsT<DQZ_NUM_LEAVES>;
+using OptArgsRb = OptArgsT<DQZ_RAINBOW_NUM_LEAVES>;
 
 struct OptScalars {
   double scale;       // clip_by_global_norm's factor (1 when inactive)
@@ -106,8 +124,8 @@ struct OptScalars {
 //   adam  m <- b1 m + (1 - b1) g;  v <- b2 v + (1 - b2) g^2
 //         theta <- theta - lr (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps)
 //   rms   nu <- d nu + (1 - d) g^2;  theta <- theta - lr g / sqrt(nu + eps)
-template <bool ADAM>
-__device__ __forceinline__ void opt_elem(const OptArgs& a, const OptScalars& s, float gf, float& th, float& m,
+template <bool ADAM, int NL>
+__device__ __forceinline__ void opt_elem(const OptArgsT<NL>& a, const OptScalars& s, float gf, float& th, float& m,
                                          float& v) {
   const double g = (double)gf * s.scale;
   if (ADAM) {
@@ -122,8 +140,8 @@ __device__ __forceinline__ void opt_elem(const OptArgs& a, const OptScalars& s, 
   }
 }
 
-template <bool ADAM>
-__device__ __forceinline__ void opt_apply_body(const OptArgs& a) {
+template <bool ADAM, int NL>
+__device__ __forceinline__ void opt_apply_body(const OptArgsT<NL>& a) {
   __shared__ OptScalars s_sc;
   __shared__ double sbuf[OPT_THREADS / 64];
   // this thread's float4s first: the loads fly while the norm is folded
@@ -172,6 +190,8 @@ __device__ __forceinline__ void opt_apply_body(const OptArgs& a) {
 
 DQZ_OTHER_KERNEL __launch_bounds__(OPT_THREADS) void opt_adam_kernel(OptArgs a) { opt_apply_body<true>(a); }
 DQZ_OTHER_KERNEL __launch_bounds__(OPT_THREADS) void opt_rms_kernel(OptArgs a) { opt_apply_body<false>(a); }
+DQZ_OTHER_KERNEL __launch_bounds__(OPT_THREADS) void opt_adam_rb_kernel(OptArgsRb a) { opt_apply_body<true>(a); }
+DQZ_OTHER_KERNEL __launch_bounds__(OPT_THREADS) void opt_rms_rb_kernel(OptArgsRb a) { opt_apply_body<false>(a); }
 
 // count <- count + 1, behind the apply that read it
 DQZ_OTHER_KERNEL void opt_count_kernel(int32_t* count) {

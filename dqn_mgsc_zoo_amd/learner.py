@@ -772,6 +772,163 @@ class C51Learner(_WideLearner):
     return (2, b, a, n)  # q_logits
 
 
+class RainbowLearner(_WideLearner):
+  """The Rainbow learner (rainbow/agent.py): the categorical head, always
+  double-Q and prioritized, behind the noisy dueling network
+  (networks.rainbow_atari_network) on device (dqz_rainbow_*).
+
+  Noise is an argument everywhere: a step reads `noise` [3, noise_len]
+  (online(s_tm1), target(s_t), online(s_t)), a forward or an actor call
+  [noise_len]; `make_noise(seed, counter)` draws it on device and advances
+  the device counter, so equal (seed, counter) give equal bits.  Its tensors
+  of the head: `support` [N] and `logits_a` [B,N]."""
+
+  _ENTRIES = dict(
+      {e: 'dqz_rainbow_' + e for e in (
+          'learner', 'optimizer_create', 'destroy', 'step', 'grad', 'outputs',
+          'profile', 'forward', 'forward_slots', 'act', 'outputs_opt')},
+      create_opt='dqz_rainbow_create', debug='dqz_rainbow_debug_head')
+  _CLASS, _NETWORK = 'RainbowLearner', 'rainbow_atari_network'
+  _SPEC = networks_lib.RainbowNetworkSpec
+  _COUNT, _GRID, _TAKEN = 'num_atoms', 'support', 'logits_a'
+  _LEARNING_RATE = 6.25e-5
+  _ALGO, _TITLE, _HEAD = 'rainbow', 'Rainbow', 'rainbow'
+  _PROFILE_SLOTS = {4: 'rb_noisy_forward', 8: 'c51_head', 2: 'rb_dhidden',
+                    5: 'rb_fc1_dx', 7: 'rb_fc_grad'}
+
+  def __init__(self, network: networks_lib.RainbowNetworkSpec, batch_size,
+               optimizer=None, device='cuda'):
+    optimizer = optimizer or chain(clip_by_global_norm(10.0),
+                                   adam(self._LEARNING_RATE, eps=0.005 / 32))
+    super().__init__(network, batch_size, optimizer, device,
+                     double_q=True, prioritized=True)
+    self.noise_len = _native.rainbow_noise_len(network.num_actions,
+                                               network.num_atoms)
+
+  def _out_shape(self, b, a, n):
+    return (3, b, a, n)  # q_logits
+
+  def make_noise(self, seed, counter, applications=3, out=None, stream=None):
+    """[applications, noise_len] of sign(t) sqrt|t|, t ~ N(0, 1) truncated to
+    [-2, 2], from Philox stream `seed` at the device uint64 `counter` [1],
+    which advances by the number of floats drawn."""
+    n = int(applications) * self.noise_len
+    if out is None:
+      out = torch.empty((int(applications), self.noise_len),
+                        dtype=torch.float32, device=self.device)
+    _native.check(_native.lib().dqz_rainbow_noise(
+        int(seed) & (2**64 - 1), _native.ptr(counter), n, _native.ptr(out),
+        _native.stream_handle(stream)))
+    return out
+
+  def _check_noise(self, noise, applications):
+    if (noise is None or noise.dtype != torch.float32 or not noise.is_cuda or
+        not noise.is_contiguous() or
+        noise.numel() != applications * self.noise_len):
+      raise ValueError('noise must be a contiguous device float32 tensor of '
+                       '%d x noise_len (%d) floats'
+                       % (applications, self.noise_len))
+
+  def _step_args(self, slots, weights, noise):
+    suffix, args = self._weighted_args(slots, weights)
+    del suffix  # always weighted: one entry
+    self._check_noise(noise, 3)
+    return args + (_native.ptr(noise),)
+
+  def step(self, store, slots, weights=None, noise=None, stream=None):  # pylint: disable=arguments-differ
+    """One learner step on `slots` with importance `weights` [B] under
+    `noise` [3, noise_len]."""
+    _native.check(self._call(
+        'step', ctypes.byref(self._params_c), store.c_ref(),
+        *self._step_args(slots, weights, noise), self._opt_h,
+        _native.ptr(self.count), _native.stream_handle(stream)))
+
+  def grad(self, store, slots, weights=None, noise=None, out=None, stream=None):  # pylint: disable=arguments-differ
+    """The step's gradient into a flat tensor (no update); padding floats keep
+    what `out` held."""
+    args = self._step_args(slots, weights, noise)
+    out = torch.zeros_like(self.online) if out is None else out
+    _native.check(self._call(
+        'grad', ctypes.byref(self._params_c), store.c_ref(), *args,
+        _native.ptr(out), _native.stream_handle(stream)))
+    return out
+
+  def apply(self, grad, stream=None):
+    """The optimizer on a finished gradient (what step does behind grad)."""
+    _native.check(_native.lib().dqz_optimizer_apply(
+        self._opt_h, _native.ptr(self.online), _native.ptr(grad),
+        _native.ptr(self.mu), _native.ptr(self.nu), _native.ptr(self.count),
+        _native.stream_handle(stream)))
+
+  def profile(self, store, slots, weights=None, noise=None, iters=20, stream=None):  # pylint: disable=arguments-differ
+    args = self._step_args(slots, weights, noise)
+    out = (ctypes.c_float * _native.NUM_PHASES)()
+    scratch = torch.zeros_like(self.online)
+    _native.check(self._call(
+        'profile', ctypes.byref(self._params_c), store.c_ref(), *args,
+        _native.ptr(scratch), int(iters), out, _native.stream_handle(stream)))
+    names = list(_native.PHASE_NAMES)
+    for slot, name in self._PROFILE_SLOTS.items():
+      names[slot] = name
+    return {n: float(t) for n, t in zip(names, out) if t > 0.0}
+
+  def fetch_noisy(self, stream=None):
+    """Diagnostic: application 0's (h_adv, h_val [B,512], adv [B,A,N], val
+    [B,N], dz_adv, dz_val [B,512]) of the last step."""
+    b, a, n = self.batch_size, self.network.num_actions, self.network.num_atoms
+    f32 = dict(dtype=torch.float32, device=self.device)
+    outs = [torch.empty(s, **f32) for s in
+            ((b, 512), (b, 512), (b, a, n), (b, n), (b, 512), (b, 512))]
+    _native.check(_native.lib().dqz_rainbow_debug(
+        self._wide, *[_native.ptr(t) for t in outs],
+        _native.stream_handle(stream)))
+    return tuple(outs)
+
+  def q_values(self, states, noise=None, params=None, stream=None):  # pylint: disable=arguments-differ
+    """q_values [n,A] of uint8 [n,84,84,4] device states under one
+    application's `noise` [noise_len] (n <= batch size)."""
+    self._check_noise(noise, 1)
+    params = self.online if params is None else params
+    states = states.contiguous()
+    n = int(states.shape[0])
+    out = torch.empty((n, self.network.num_actions), dtype=torch.float32,
+                      device=self.device)
+    _native.check(self._call(
+        'forward', _native.ptr(params), _native.ptr(states), n,
+        _native.ptr(noise), _native.ptr(out), _native.stream_handle(stream)))
+    return out
+
+  def q_values_slots(self, store, slots, which, noise=None, params=None, stream=None):  # pylint: disable=arguments-differ
+    self._check_noise(noise, 1)
+    params = self.online if params is None else params
+    n = int(slots.numel())
+    out = torch.empty((n, self.network.num_actions), dtype=torch.float32,
+                      device=self.device)
+    _native.check(self._call(
+        'forward_slots', _native.ptr(params), store.c_ref(), _native.ptr(slots),
+        n, int(which), _native.ptr(noise), _native.ptr(out),
+        _native.stream_handle(stream)))
+    return out
+
+  def act(self, observation, noise, params=None):  # pylint: disable=arguments-differ
+    """(argmax_a q, max_a q) of one host uint8 [84,84,4] observation under
+    `noise` [noise_len]: no epsilon (rainbow/agent.py: the noise explores)."""
+    self._check_noise(noise, 1)
+    if self._act_in is None:
+      self._act_in = torch.empty((1, 84, 84, 4), dtype=torch.uint8,
+                                 pin_memory=True)
+      self._act_in_np = self._act_in.numpy()
+      self._act_out = torch.zeros((2,), dtype=torch.int32, pin_memory=True)
+      self._act_out_np = self._act_out.numpy()
+    self._act_in_np[0] = observation
+    _native.check(self._call(
+        'act', _native.ptr(self._params_tensor(params)),
+        ctypes.c_void_p(self._act_in.data_ptr()), 1, _native.ptr(noise),
+        ctypes.c_void_p(self._act_out.data_ptr()), _native.stream_handle()))
+    torch.cuda.current_stream(self.device).synchronize()
+    return int(self._act_out_np[0]), float(self._act_out_np.view(np.float32)[1])
+
+
 def check_huber_param(huber_param):
   """The quantile head's huber_param as a float; 0 is refused by name."""
   huber_param = float(huber_param)

@@ -236,3 +236,90 @@ class QRNetworkSpec(WideNetworkSpec):
 def qr_atari_network(num_actions: int, quantiles) -> QRNetworkSpec:
   """QR-DQN network, expects uint8 input (networks.py:295-313)."""
   return QRNetworkSpec(num_actions, quantiles)
+
+
+_RB_TORSO = 'sequential'
+# The noisy linears in call order: (module suffix, fan_in, outputs-fn(A, N), mu has a bias)
+_RB_NOISY = (
+    ('', 3136, lambda a, n: 512, True),        # advantage, hidden
+    ('_1', 512, lambda a, n: a * n, False),    # advantage, output
+    ('_2', 3136, lambda a, n: 512, True),      # value, hidden
+    ('_3', 512, lambda a, n: n, False),        # value, output
+)
+
+
+class RainbowNetworkSpec(C51NetworkSpec):
+  """NetworkSpec of the Rainbow network (networks.py:137-178, 224-261): the DQN
+  torso, then two streams of two noisy linear layers each,
+
+    noisy(x) = x Wmu + bmu + ((e_in * x) Wsig + bsig) * e_out,
+
+  advantage 3136 -> 512 -> A * N and value 3136 -> 512 -> N (the output
+  layers' mu without a bias, sigma always with one), combined as
+  q_logits = value + advantage - mean_a advantage.
+
+  Twenty leaves in the device order of `_native.rainbow_param_layout`.  The
+  noisy linears are named as Haiku numbers the reference's anonymous `mu` /
+  `sigma` modules in call order: `mu`, `sigma`, `mu_1`, `sigma_1`, `mu_2`,
+  `sigma_2`, `mu_3`, `sigma_3`, each with `w` (and `b`), and the torso's
+  convolutions sit in `sequential`.  Haiku is not installed here, so these
+  names are not pinned against a reference checkpoint.
+
+  `noise_len` floats of noise feed one application (`_native.rainbow_noise_len`:
+  8320 + A N + N), in the reference's draw order."""
+
+  def __new__(cls, num_actions, support, noisy_weight_init):
+    self = super().__new__(cls, num_actions, support)
+    self.noisy_weight_init = float(noisy_weight_init)
+    return self
+
+  def _fc_leaves(self):
+    """(module, name, shape, fan_in, is_sigma) of the fourteen fc leaves."""
+    a, n = self.num_actions, self.num_atoms
+    out = []
+    for suffix, fan_in, outputs, mu_bias in _RB_NOISY:
+      width = outputs(a, n)
+      out.append(('mu' + suffix, 'w', (fan_in, width), fan_in, False))
+      if mu_bias:
+        out.append(('mu' + suffix, 'b', (width,), fan_in, False))
+      out.append(('sigma' + suffix, 'w', (fan_in, width), fan_in, True))
+      out.append(('sigma' + suffix, 'b', (width,), fan_in, True))
+    return out
+
+  def leaf_paths(self):
+    torso = [(_RB_TORSO + mod[len(_TORSO):], name) for mod, name, _, _ in _LEAVES[:6]]
+    return torso + [(mod, name) for mod, name, _, _, _ in self._fc_leaves()]
+
+  def leaf_shapes(self):
+    torso = [shape_fn(0) for _, _, shape_fn, _ in _LEAVES[:6]]
+    return torso + [shape for _, _, shape, _, _ in self._fc_leaves()]
+
+  def layout(self):
+    return _native.rainbow_param_layout(self.num_actions, self.num_atoms)
+
+  @property
+  def noise_len(self):
+    return 8320 + self.num_actions * self.num_atoms + self.num_atoms
+
+  def init(self, seed=0):
+    """mu ~ U(+-1/sqrt(fan_in)) (the DQN initialiser), sigma the constant
+    noisy_weight_init / sqrt(fan_in), float32."""
+    rng = np.random.default_rng(seed)
+    fans = [f for _, _, _, f in _LEAVES[:6]] + [f for _, _, _, f, _ in self._fc_leaves()]
+    sigma = [False] * 6 + [s for _, _, _, _, s in self._fc_leaves()]
+    tree = collections.OrderedDict()
+    for (mod, name), shape, fan_in, is_sigma in zip(
+        self.leaf_paths(), self.leaf_shapes(), fans, sigma):
+      if is_sigma:
+        leaf = np.full(shape, self.noisy_weight_init / np.sqrt(fan_in), np.float32)
+      else:
+        bound = np.sqrt(1.0 / fan_in)
+        leaf = rng.uniform(-bound, bound, size=shape).astype(np.float32)
+      tree.setdefault(mod, collections.OrderedDict())[name] = leaf
+    return tree
+
+
+def rainbow_atari_network(num_actions: int, support,
+                          noisy_weight_init: float) -> RainbowNetworkSpec:
+  """Rainbow network, expects uint8 input (networks.py:224-261)."""
+  return RainbowNetworkSpec(num_actions, support, noisy_weight_init)

@@ -3,10 +3,10 @@ dqn_zoo/rainbow/agent.py:85-150 (rlax.categorical_double_q_learning, the loss
 weighted by the replay's importance weights, clip(|loss_b|, 0, 100) written
 back as the priority) on `networks.c51_atari_network`.
 
-What Rainbow has beyond this is its network (noisy, dueling), which is not
-built: these networks have no noisy layers, so acting stays eps-greedy and the
-constructor is the C51 agent's, with `double_q` (on by default; off gives plain
-prioritized C51).  The replay is a PrioritizedTransitionReplay and the
+What Rainbow has beyond this is its network (noisy, dueling), which is
+`rainbow/agent.py`'s: this agent's network has no noisy layers, so acting stays
+eps-greedy and the constructor is the C51 agent's, with `double_q` (on by
+default; off gives plain prioritized C51).  The replay is a PrioritizedTransitionReplay and the
 transitions usually come from replay.NStepTransitionAccumulator.
 """
 

@@ -803,6 +803,75 @@ int dqz_c51_outputs_opt(dqz_c51* c51, float* q_selector, float* priorities, void
 /* dqz_c51_debug_check for a head created with `options`. */
 int dqz_c51_debug_check_opt(int batch, unsigned request, const dqz_wide_options* options);
 
+/* ---- the Rainbow agent (rainbow/agent.py; networks.py rainbow_atari_network) --
+ * The categorical head with double_q and weighted both set, behind a noisy
+ * dueling network.  x = flatten(conv3) [B, 3136] (post-ReLU), then
+ *   noisy(x) = x Wmu + bmu + ((e_in * x) Wsig + bsig) * e_out
+ *   h_adv = relu(noisy_A1(x))   adv = noisy_A2(h_adv)  [A N], mu without a bias
+ *   h_val = relu(noisy_V1(x))   val = noisy_V2(h_val)  [N],   mu without a bias
+ *   q_logits[b, a, n] = val[b, n] + adv[b, a, n] - mean_a' adv[b, a', n].
+ * The noise comes from the caller: one application of the network reads one
+ * vector of dqz_rainbow_noise_len(A, N) = 8320 + A N + N floats, in the order
+ *   A1_in 3136 | A1_out 512 | A2_in 512 | A2_out A N | V1_in 3136 | V1_out 512 |
+ *   V2_in 512 | V2_out N,
+ * and a learner step three of them, [3][noise_len]: online(s_tm1) (the only
+ * differentiated application), target(s_t), online(s_t) (the selector).  No
+ * entry but dqz_rainbow_noise draws noise, so equal noise gives equal bits.
+ * Parameter layout, DQZ_RAINBOW_NUM_LEAVES leaves, each padded to 64 floats:
+ *   0-5 the conv leaves   6 A1 mu/w [3136,512]  7 A1 mu/b [512]
+ *   8 A1 sigma/w  9 A1 sigma/b  10 A2 mu/w [512, A N]  11 A2 sigma/w  12 A2 sigma/b [A N]
+ *   13 V1 mu/w  14 V1 mu/b  15 V1 sigma/w  16 V1 sigma/b  17 V2 mu/w [512, N]
+ *   18 V2 sigma/w  19 V2 sigma/b [N].
+ * Limits are the categorical head's: batch 2..256, A 1..32, N 2..64, A N <=
+ * 1024.  The step is always double-Q and weighted and runs in gradient mode
+ * followed by the optimizer; it refuses, in the wide heads' words, every
+ * in-launch draw, the fused prioritized draw, the fused write-back, the MGSC
+ * modes, the unit cotangent and fused centered RMSProp. */
+#define DQZ_RAINBOW_NUM_LEAVES 20
+typedef struct dqz_rainbow dqz_rainbow;
+int dqz_rainbow_param_layout(int num_actions, int num_atoms, int64_t offsets[DQZ_RAINBOW_NUM_LEAVES],
+                             int64_t sizes[DQZ_RAINBOW_NUM_LEAVES], int64_t* total);
+int dqz_rainbow_noise_len(int num_actions, int num_atoms, int* out);
+/* out[i] = sign(t) sqrt|t|, t = sqrt(2) erfinv(lo + u_i (hi - lo)), lo / hi =
+ * erf(-/+ sqrt(2)) (a standard normal truncated to [-2, 2]) and u_i the i-th
+ * uniform dqz_uniform_philox(seed, counter) gives; *counter_dev += n on device.
+ * 1 <= n <= 65536; out device f32 [n]. */
+int dqz_rainbow_noise(uint64_t seed, uint64_t* counter_dev, int n, float* out, void* stream);
+int dqz_rainbow_optimizer_create(const dqz_optimizer_config* cfg, int num_atoms, dqz_optimizer** out);
+/* options: NULL or {1, 1}; anything else is refused (there is no plain Rainbow). */
+int dqz_rainbow_create(const dqz_learner_config* cfg, int num_atoms, const float* support,
+                       const dqz_wide_options* options, dqz_rainbow** out);
+int dqz_rainbow_destroy(dqz_rainbow* rb);
+int dqz_rainbow_learner(dqz_rainbow* rb, dqz_learner** out);
+/* is_weights: device f32 [B]; noise: device f32 [3][noise_len]; both refused
+ * before any device call when null. */
+int dqz_rainbow_step(dqz_rainbow* rb, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                     const float* is_weights, const float* noise, dqz_optimizer* opt, int32_t* count, void* stream);
+int dqz_rainbow_grad(dqz_rainbow* rb, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                     const float* is_weights, const float* noise, float* grad_out, void* stream);
+int dqz_rainbow_profile(dqz_rainbow* rb, const dqz_params* params, const dqz_store* store, const int32_t* slots,
+                        const float* is_weights, const float* noise, float* grad_out, int iters, float* phase_ms,
+                        void* stream);
+/* dqz_c51_outputs / dqz_c51_outputs_opt / dqz_c51_debug of the step's head. */
+int dqz_rainbow_outputs(dqz_rainbow* rb, float* logits_a, float* q_values, float* loss_b, float* loss,
+                        int32_t* a_star, void* stream);
+int dqz_rainbow_outputs_opt(dqz_rainbow* rb, float* q_selector, float* priorities, void* stream);
+int dqz_rainbow_debug_head(dqz_rainbow* rb, float* q_logits, float* dlogits, void* stream);
+/* Diagnostic: application 0's h_adv, h_val [B][512], adv [B][A N], val [B][N]
+ * and dz_adv, dz_val [B][512] of the last step (any may be NULL). */
+int dqz_rainbow_debug(dqz_rainbow* rb, float* h_adv, float* h_val, float* adv, float* val, float* dz_adv,
+                      float* dz_val, void* stream);
+/* q_values [n][A] of one application (noise [noise_len]); act: the argmax and
+ * v_t = max_a q per state, no epsilon (states and out may be pinned host memory). */
+int dqz_rainbow_forward(dqz_rainbow* rb, const float* params, const uint8_t* states, int n, const float* noise,
+                        float* q_out, void* stream);
+int dqz_rainbow_forward_slots(dqz_rainbow* rb, const float* params, const dqz_store* store, const int32_t* slots,
+                              int n, int which, const float* noise, float* q_out, void* stream);
+int dqz_rainbow_act(dqz_rainbow* rb, const float* params, const uint8_t* states, int n, const float* noise,
+                    dqz_action* out, void* stream);
+/* dqz_c51_debug_check for a Rainbow request (DQZ_C51_REQ_* bits).  No device call. */
+int dqz_rainbow_debug_check(int batch, unsigned request);
+
 /* ---- the quantile (QR-DQN) agent (qrdqn/agent.py:36-39,88-134) ------------
  * networks.qr_atari_network (networks.py:295-313): the NatureQNetwork torso
  * with a last layer N * A wide, N quantile values per action, quantile-major:

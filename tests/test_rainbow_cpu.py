@@ -1,0 +1,143 @@
+"""The Rainbow network's reference and spec, without a GPU: tests/rainbow_ref
+against torch autograd written in the reference's own order (mu(x) +
+sigma(e_in x) e_out), the dueling combine's known answers, and
+networks.rainbow_atari_network's leaves, sizes and initialisation."""
+
+import numpy as np
+import pytest
+import torch
+
+from dqn_mgsc_zoo_amd import networks
+from tests import c51_ref
+from tests import rainbow_ref
+
+A, N, B = 3, 5, 3
+
+
+def _batch(rng, b, a):
+  s_tm1 = rng.integers(0, 256, size=(b, 84, 84, 4), dtype=np.uint8)
+  s_t = rng.integers(0, 256, size=(b, 84, 84, 4), dtype=np.uint8)
+  return (s_tm1, rng.integers(0, a, size=b), rng.choice([-1.0, 0.0, 1.0], size=b),
+          np.full(b, 0.99), s_t)
+
+
+def _sigma_up(tree, factor=20.0):
+  """Sigma leaves large enough that a wrong noise term moves the result."""
+  for mod in tree:
+    if mod.startswith('sigma'):
+      for k in tree[mod]:
+        tree[mod][k] = tree[mod][k] * factor
+  return tree
+
+
+def _torch_network(p, s, noise, a, n):
+  """q_logits [B, A, N] in torch float64, layer by layer as networks.py does."""
+  x = torch.from_numpy(np.asarray(s)).double().div(255.0).permute(0, 3, 1, 2)
+  for name, stride in zip(rainbow_ref.TORSO, (4, 2, 1)):
+    w = p[name]['w'].permute(3, 2, 0, 1)  # HWIO -> OIHW
+    x = torch.relu(torch.nn.functional.conv2d(x, w, p[name]['b'], stride=stride))
+  x = x.permute(0, 2, 3, 1).reshape(x.shape[0], -1)
+
+  def noisy(inputs, layer):
+    mu, sig, mu_bias = rainbow_ref.LAYERS[layer]
+    e_in, e_out = (torch.from_numpy(e) for e in noise[layer])
+    out = inputs @ p[mu]['w']
+    if mu_bias:
+      out = out + p[mu]['b']
+    return out + ((e_in * inputs) @ p[sig]['w'] + p[sig]['b']) * e_out
+
+  adv = noisy(torch.relu(noisy(x, 'a1')), 'a2').reshape(-1, a, n)
+  val = noisy(torch.relu(noisy(x, 'v1')), 'v2').reshape(-1, 1, n)
+  return val + adv - adv.mean(dim=1, keepdim=True)
+
+
+def test_ref_gradient_matches_autograd_on_every_leaf():
+  rng = np.random.default_rng(0)
+  support = c51_ref.make_support(10.0, N)
+  net = networks.rainbow_atari_network(A, support, 0.1)
+  online = _sigma_up(net.init(1))
+  target = _sigma_up(net.init(2))
+  batch = _batch(rng, B, A)
+  noise3 = rainbow_ref.make_noise(rng, 3, A, N)
+  weights = rng.uniform(0.2, 1.0, size=B)
+  res = rainbow_ref.learner_grads(online, target, batch, noise3, support, A, weights)
+
+  p = {m: {k: torch.tensor(np.asarray(v, np.float64), requires_grad=True)
+           for k, v in d.items()} for m, d in online.items()}
+  logits = _torch_network(p, batch[0], rainbow_ref.split_noise(noise3[0], A, N), A, N)
+  np.testing.assert_allclose(logits.detach().numpy(), res['out'][0], rtol=0, atol=1e-10)
+  la = logits[torch.arange(B), torch.from_numpy(np.asarray(batch[1]))]
+  m = torch.from_numpy(res['m'])  # the projected target, under stop_gradient
+  loss_b = -(m * torch.log_softmax(la, dim=-1)).sum(dim=-1)
+  np.testing.assert_allclose(loss_b.detach().numpy(), res['loss_b'], rtol=1e-10)
+  (torch.from_numpy(weights) * loss_b).mean().backward()
+  paths = net.leaf_paths()
+  assert len(paths) == 20
+  for mod, name in paths:
+    got, want = res['grads'][mod][name], p[mod][name].grad.numpy()
+    assert got.shape == want.shape, (mod, name)
+    assert np.abs(want).max() > 0, (mod, name)
+    np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-12 * np.abs(want).max() + 1e-18,
+                               err_msg='%s/%s' % (mod, name))
+
+
+def test_dueling_known_answers():
+  rng = np.random.default_rng(1)
+  adv, val = rng.normal(size=(4, 6, 7)), rng.normal(size=(4, 7))
+  q = rainbow_ref.dueling(adv, val)
+  np.testing.assert_allclose((q - val[:, None, :]).mean(axis=1), 0.0, atol=1e-15)
+  one = rainbow_ref.dueling(adv[:, :1], val)  # A = 1: no advantage left
+  np.testing.assert_allclose(one[:, 0], val, rtol=0, atol=1e-15)
+
+
+def test_effective_weights_with_zero_noise_are_mu():
+  support = c51_ref.make_support(10.0, N)
+  net = networks.rainbow_atari_network(A, support, 0.1)
+  params = net.init(0)
+  zero = rainbow_ref.split_noise(np.zeros(rainbow_ref.noise_len(A, N)), A, N)
+  eff = rainbow_ref.effective(params, zero)
+  for layer, (mu, _, mu_bias) in rainbow_ref.LAYERS.items():
+    np.testing.assert_array_equal(eff[layer][0], params[mu]['w'])
+    np.testing.assert_array_equal(eff[layer][1], params[mu]['b'] if mu_bias else 0.0)
+
+
+@pytest.mark.parametrize('a,n', [(1, 2), (3, 51), (18, 51), (16, 64)])
+def test_spec_leaves_sizes_and_noise_len(a, n):
+  net = networks.rainbow_atari_network(a, c51_ref.make_support(10.0, n), 0.1)
+  shapes = net.leaf_shapes()
+  assert len(shapes) == len(net.leaf_paths()) == 20
+  fc = [(3136, 512), (512,), (3136, 512), (512,), (512, a * n), (512, a * n), (a * n,),
+        (3136, 512), (512,), (3136, 512), (512,), (512, n), (512, n), (n,)]
+  assert shapes[6:] == fc
+  assert [p for p in net.leaf_paths()[6:]] == [
+      ('mu', 'w'), ('mu', 'b'), ('sigma', 'w'), ('sigma', 'b'),
+      ('mu_1', 'w'), ('sigma_1', 'w'), ('sigma_1', 'b'),
+      ('mu_2', 'w'), ('mu_2', 'b'), ('sigma_2', 'w'), ('sigma_2', 'b'),
+      ('mu_3', 'w'), ('sigma_3', 'w'), ('sigma_3', 'b')]
+  conv = 8 * 8 * 4 * 32 + 32 + 4 * 4 * 32 * 64 + 64 + 3 * 3 * 64 * 64 + 64
+  want = conv + 4 * 3136 * 512 + 4 * 512 + 2 * 512 * a * n + a * n + 2 * 512 * n + n
+  assert net.num_params == want
+  assert net.noise_len == 8320 + a * n + n == rainbow_ref.noise_len(a, n)
+  offsets, sizes, total = net.layout()
+  assert sizes == [int(np.prod(s)) for s in shapes]
+  assert all(o % 64 == 0 for o in offsets) and total % 64 == 0
+  assert all(offsets[i] + sizes[i] <= offsets[i + 1] for i in range(19))
+  assert offsets[19] + sizes[19] <= total
+  # A1-mu sits where fc1 does in every other network of the project
+  assert offsets[:8] == networks.dqn_atari_network(a).layout()[0][:8]
+
+
+def test_sigma_init_is_the_constant_and_mu_is_bounded():
+  net = networks.rainbow_atari_network(4, c51_ref.make_support(10.0, 51), 0.1)
+  tree = net.init(3)
+  for layer, (mu, sig, mu_bias) in rainbow_ref.LAYERS.items():
+    fan_in = tree[mu]['w'].shape[0]
+    const = np.float32(0.1 / np.sqrt(fan_in))
+    assert np.all(tree[sig]['w'] == const) and np.all(tree[sig]['b'] == const), layer
+    bound = 1.0 / np.sqrt(fan_in)
+    assert np.abs(tree[mu]['w']).max() <= bound and tree[mu]['w'].std() > 0.4 * bound
+    assert ('b' in tree[mu]) == mu_bias
+  flat = net.flatten(tree)
+  back = net.unflatten(flat)
+  for mod, name in net.leaf_paths():
+    np.testing.assert_array_equal(back[mod][name], tree[mod][name])
