@@ -931,20 +931,39 @@ int dqz_learner_debug_activations(dqz_learner* L, int z, float* y1, float* y2, f
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
-// the categorical (C51) and quantile (QR-DQN) agents (c51.hpp, qr.hpp): one host path, two sets of entries
+// the categorical (C51), quantile (QR-DQN) and Rainbow agents (c51.hpp, qr.hpp, rainbow.hpp): one host path, three
+// sets of entries (Rainbow's own launches and entries: the next section)
 
 static_assert(C51_MAX_ATOMS == C51_MAXN && C51_MAX_OUT == C51_MAXOUT, "learner_impl.hpp restates c51.hpp's limits");
 static_assert(QR_MAX_QUANTILES == QR_MAXN && QR_MAX_OUT == QR_MAXOUT, "learner_impl.hpp restates qr.hpp's limits");
 
-// A dqz_learner on the wide layout plus the head's own buffers: what a dqz_c51 and a dqz_qr handle point to.
+// The Rainbow agent's noisy dueling network in front of the categorical head (rainbow.hpp): its leaves, noise
+// layout, twenty-leaf parameter layout and scratch.  Of the inner learner's buffers fc1p holds A1-mu's partials,
+// h1 is h_adv, dz1 is dz_adv and dy3 the combined dX, so the step's own fc1 dW and update find A1-mu as fc1.
+struct dqz::RbNet {
+  RbLeaves lf;
+  RbNoise nl;
+  int64_t off[DQZ_RAINBOW_NUM_LEAVES], sz[DQZ_RAINBOW_NUM_LEAVES], total;
+  float* ys;                            // [2][Z][B][3136] e_in * y3 of A1 and of V1
+  float* part[3];                       // [Z][S][B][512] split-K partials of V1-mu, A1-sigma, V1-sigma
+  float *h_val, *adv, *val;             // [Z][B][512], [Z][B][A N], [Z][B][N]
+  float *dz_val, *dz_adv_e, *dz_val_e;  // [B][512]
+  float* dx;                            // [4][B][3136]
+  void* block;
+};
+
+// A dqz_learner on the wide layout plus the head's own buffers: what a dqz_c51, a dqz_qr and a dqz_rainbow handle
+// point to.
 struct dqz_wide {
   dqz_learner* L;
   int A, N;
   WideHead head;  // grid and outputs, carved from block
+  RbNet* rb;      // WIDE_RB alone (head.rb is its view of it); null otherwise
   void* block;
 };
 static dqz_wide* wide_of(dqz_c51* C) { return reinterpret_cast<dqz_wide*>(C); }
 static dqz_wide* wide_of(dqz_qr* Q) { return reinterpret_cast<dqz_wide*>(Q); }
+static dqz_wide* wide_of(dqz_rainbow* R) { return reinterpret_cast<dqz_wide*>(R); }
 static dqz_learner* learner_of(dqz_wide* W) { return W ? W->L : nullptr; }  // null: the shared checks refuse it
 
 static int wide_check_shape(WideKind kind, int A, int N) {
@@ -1000,16 +1019,19 @@ static QrHeadArgs qr_head_args(const WideHead& c, int Z, int B, int A) {
   return h;
 }
 
+// The noisy network's launches (below, behind the entries' shared bodies)
+static int rb_outputs(dqz_learner* L, const WideHead& c, const NetZ& nz, int Z, int B, const float* noise,
+                      hipStream_t st);
 static int rb_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, hipStream_t st);
 
 int dqz::wide_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const WideHead& c = *r.wide;
-  const bool qr = c.kind == WIDE_QR;
+  const bool qr = c.kind == WIDE_QR, rb = c.kind == WIDE_RB;
   const int B = L->cfg.batch, A = L->cfg.num_actions, N = c.N;
   const int Z = L->Z;  // 3 with double_q: the selector, online(s_t), is copy 2
-  const int mode = (c.double_q ? WIDE_DOUBLE : 0) | (c.weighted ? WIDE_WEIGHTED : 0);
-  if (c.kind == WIDE_RB) return rb_launch(which, L, P, r, st);
+  const int mode = (c.double_q ? WIDE_DOUBLE : 0) | (c.weighted ? WIDE_WEIGHTED : 0) | (rb ? WIDE_NO_DZ1 : 0);
+  if (rb && which != WIDE_HEAD) return rb_launch(which, L, P, r, st);  // its head is the categorical one, below
   if (which == WIDE_OUTPUTS) {
     const NetZ nz{{P->online, P->target, P->online}, {0, 1, 1}};
     return c51_logits(L, nz, Z, B, A * N, c.out, st);
@@ -1031,10 +1053,13 @@ int dqz::wide_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, cons
     auto* const k = mode == 3 ? qr_head_kernel<3> : mode == 2 ? qr_head_kernel<2>
                   : mode == 1 ? qr_head_kernel<1> : qr_head_kernel<0>;
     hipLaunchKernelGGL(k, dim3(B), dim3(QR_THREADS), 0, st, h);
-  } else if (which == WIDE_HEAD) {
+  } else if (which == WIDE_HEAD) {  // plain, or behind the noisy network
     C51HeadArgs h = c51_head_args(c, Z, B, A);
-    h.h1 = L->h1;
-    h.w2 = P->online + L->off[8];
+    if (!rb) {  // WIDE_NO_DZ1: dz is rb_dhidden_kernel's (WIDE_DZ1), and h1, w2 and dz1 stay unset
+      h.h1 = L->h1;
+      h.w2 = P->online + L->off[8];
+      h.dz1 = L->dz1;
+    }
     h.rec = reinterpret_cast<const float4*>(L->rec);
     h.qv = c.qv;
     h.la = c.taken;
@@ -1043,11 +1068,13 @@ int dqz::wide_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, cons
     h.loss_part = L->loss_part;
     h.gq = L->gq;
     h.ga = L->ga;
-    h.dz1 = L->dz1;
     h.weights = r.is_weights;
     h.loss_b = c.loss_b;
     h.prio = L->td;
-    auto* const k = mode == 3 ? c51_head_kernel<3> : mode == 2 ? c51_head_kernel<2>
+    // a Rainbow head is double_q and weighted (dqz_rainbow_create): 7 is its one mode, the only one built with
+    // WIDE_NO_DZ1; no other may fall through to a kernel that reads the h1, w2 and dz1 left unset above
+    if (rb && mode != 7) return fail(DQZ_ERR_INVALID, "the rainbow head is built double-Q and weighted only");
+    auto* const k = mode == 7 ? c51_head_kernel<7> : mode == 3 ? c51_head_kernel<3> : mode == 2 ? c51_head_kernel<2>
                   : mode == 1 ? c51_head_kernel<1> : c51_head_kernel<0>;
     hipLaunchKernelGGL(k, dim3(B), dim3(HID), 0, st, h);
   } else if (which == WIDE_DZ1) {  // the quantile head alone (WideHead::dout)
@@ -1101,13 +1128,21 @@ static void set_forward(Args* h, float* q_out, const ActorDraw* act) {
   }
 }
 
-// q_values of n states through one copy: the torso, the outputs, the head in forward mode (actor: with a draw)
-static int wide_forward_q(dqz_wide* W, const float* params, const Conv1Src& src, int which, int n, float* q_out,
-                          const ActorDraw* act, hipStream_t st) {
+// q_values of n states through one copy: the torso, the outputs (a WIDE_RB head's: one application of the noisy
+// network under `noise` [len], null from the others), the head in forward mode (actor: with a draw)
+static int wide_forward_q(dqz_wide* W, const float* params, const Conv1Src& src, int which, int n, const float* noise,
+                          float* q_out, const ActorDraw* act, hipStream_t st) {
   dqz_learner* L = W->L;
+  const bool rb = W->head.kind == WIDE_RB;
+  // the noisy network's launches read the parameters as float4: refused before the torso; the others' outputs
+  // launch alone does, and c51_logits refuses there
+  if (rb && reinterpret_cast<uintptr_t>(params) % 16)
+    return fail(DQZ_ERR_INVALID, "parameters must be 16-byte aligned");
   if (int rc = forward_torso(L, params, src, which, n, st)) return rc;
   const NetZ nz{{params, params, params}, {which, which, which}};
-  if (int rc = c51_logits(L, nz, 1, n, W->A * W->N, W->head.out, st)) return rc;
+  if (int rc = rb ? rb_outputs(L, W->head, nz, 1, n, noise, st)
+                  : c51_logits(L, nz, 1, n, W->A * W->N, W->head.out, st))
+    return rc;
   if (W->head.kind == WIDE_QR) {
     QrHeadArgs h = qr_head_args(W->head, 1, n, W->A);
     set_forward(&h, q_out, act);
@@ -1135,7 +1170,8 @@ static int wide_optimizer_create(WideKind kind, const dqz_optimizer_config* cfg,
   if (!cfg || !out) return fail(DQZ_ERR_INVALID, "null argument");
   if (int rc = wide_check_shape(kind, cfg->num_actions, N)) return rc;
   if (cfg->shared_bias) return fail(DQZ_ERR_INVALID, "the %s head has no shared bias", kWide[kind].noun);
-  return optimizer_create(cfg, N, out);  // the wide layout depends on A * N alone
+  // the wide layout depends on A * N alone; the Rainbow network's is the twenty-leaf one
+  return optimizer_create(cfg, N, out, kind == WIDE_RB);
 }
 
 // What a create refuses of its configuration before it reads the grid: cfg is non-null
@@ -1148,6 +1184,8 @@ static int wide_check_config(WideKind kind, const dqz_learner_config* cfg, int N
 
 static int wide_destroy(dqz_wide* W) {
   if (!W) return DQZ_OK;
+  if (W->rb && W->rb->block) (void)hipFree(W->rb->block);
+  delete W->rb;
   if (W->block) (void)hipFree(W->block);
   (void)dqz_learner_destroy(W->L);
   delete W;
@@ -1181,9 +1219,7 @@ static int wide_create(WideKind kind, const dqz_learner_config* cfg, int N, cons
   const int64_t floats = n_grid + n_out + 2 * n_tk + n_do + n_qv + n_as + n_lb;
   if (hipMalloc(&W->block, floats * sizeof(float)) != hipSuccess ||
       hipMemset(W->block, 0, floats * sizeof(float)) != hipSuccess) {
-    if (W->block) (void)hipFree(W->block);
-    (void)dqz_learner_destroy(L);
-    delete W;
+    (void)wide_destroy(W);
     return fail(DQZ_ERR_HIP, "hipMalloc of %lld bytes of %s-head scratch failed", (long long)(floats * 4), d.noun);
   }
   float* p = (float*)W->block;
@@ -1215,27 +1251,30 @@ static int wide_learner(dqz_wide* W, dqz_learner** out) {
   return DQZ_OK;
 }
 
-// is_weights: null from the plain entries; the _w entries have refused a null one
+// is_weights: null from the plain entries; the _w entries have refused a null one.  noise: [3][len], null from
+// every head but Rainbow's, whose entries have refused a null one.
 static int wide_step(dqz_wide* W, const dqz_params* P, const dqz_store* S, const int32_t* slots,
-                     const float* is_weights, dqz_optimizer* o, int32_t* count, void* stream) {
+                     const float* is_weights, const float* noise, dqz_optimizer* o, int32_t* count, void* stream) {
   if (!W) return fail(DQZ_ERR_INVALID, "null argument");
-  return step_then_apply(W->L, P, S, {.slots = slots, .is_weights = is_weights, .wide = &W->head}, o, count, stream);
+  const StepRequest r{.slots = slots, .is_weights = is_weights, .wide = &W->head, .noise = noise};
+  return step_then_apply(W->L, P, S, r, o, count, stream);
 }
 
 static int wide_grad(dqz_wide* W, const dqz_params* P, const dqz_store* S, const int32_t* slots,
-                     const float* is_weights, float* grad_out, void* stream) {
+                     const float* is_weights, const float* noise, float* grad_out, void* stream) {
   if (!W) return fail(DQZ_ERR_INVALID, "null argument");
   if (!grad_out) return fail(DQZ_ERR_INVALID, "null grad_out");
-  return step_impl(W->L, P, S, {.slots = slots, .is_weights = is_weights, .gout = grad_out, .wide = &W->head},
-                   stream);
+  const StepRequest r{.slots = slots, .is_weights = is_weights, .gout = grad_out, .wide = &W->head, .noise = noise};
+  return step_impl(W->L, P, S, r, stream);
 }
 
 static int wide_profile(dqz_wide* W, const dqz_params* P, const dqz_store* S, const int32_t* slots,
-                        const float* is_weights, float* grad_out, int iters, float* phase_ms, void* stream) {
+                        const float* is_weights, const float* noise, float* grad_out, int iters, float* phase_ms,
+                        void* stream) {
   if (!W) return fail(DQZ_ERR_INVALID, "null argument");
   if (!grad_out) return fail(DQZ_ERR_INVALID, "null grad_out");
-  return profile_step(W->L, P, S, {.slots = slots, .is_weights = is_weights, .gout = grad_out, .wide = &W->head},
-                      iters, phase_ms, stream);
+  const StepRequest r{.slots = slots, .is_weights = is_weights, .gout = grad_out, .wide = &W->head, .noise = noise};
+  return profile_step(W->L, P, S, r, iters, phase_ms, stream);
 }
 
 static int wide_check_weights(const void* handle, const float* is_weights) {
@@ -1285,26 +1324,35 @@ static int wide_debug(dqz_wide* W, float* outputs, float* dtaken, void* stream) 
   return DQZ_OK;
 }
 
-static int wide_forward(dqz_wide* W, const float* params, const uint8_t* states, int n, float* q_out, void* stream) {
+// noise: [len], null from every head but Rainbow's, whose entries have refused a null one
+static int wide_forward(dqz_wide* W, const float* params, const uint8_t* states, int n, const float* noise,
+                        float* q_out, void* stream) {
   Conv1Src src;
   if (int rc = forward_src(learner_of(W), params, n, {.states = states, .q_out = q_out}, &src)) return rc;
-  return wide_forward_q(W, params, src, 0, n, q_out, nullptr, (hipStream_t)stream);
+  return wide_forward_q(W, params, src, 0, n, noise, q_out, nullptr, (hipStream_t)stream);
 }
 
 static int wide_forward_slots(dqz_wide* W, const float* params, const dqz_store* S, const int32_t* slots, int n,
-                              int which, float* q_out, void* stream) {
+                              int which, const float* noise, float* q_out, void* stream) {
   Conv1Src src;
   const ForwardInput in{.from_store = true, .store = S, .slots = slots, .which = which, .q_out = q_out};
   if (int rc = forward_src(learner_of(W), params, n, in, &src)) return rc;
-  return wide_forward_q(W, params, src, which, n, q_out, nullptr, (hipStream_t)stream);
+  return wide_forward_q(W, params, src, which, n, noise, q_out, nullptr, (hipStream_t)stream);
 }
 
-static int wide_act(dqz_wide* W, const float* params, const uint8_t* states, int n, double epsilon, uint64_t seed,
-                    uint64_t counter, dqz_action* out, void* stream) {
+// The Rainbow actor has no epsilon (its entry passes 0): the noise explores, and behind the head in plain forward
+// mode rb_act_kernel takes the first argmax with no draw (eps_greedy at eps = 0 breaks ties by its uniform).
+static int wide_act(dqz_wide* W, const float* params, const uint8_t* states, int n, const float* noise,
+                    double epsilon, uint64_t seed, uint64_t counter, dqz_action* out, void* stream) {
   ActorDraw act{epsilon, seed, counter, out};
   Conv1Src src;
   if (int rc = forward_src(learner_of(W), params, n, {.states = states, .act = &act}, &src)) return rc;
-  return wide_forward_q(W, params, src, 0, n, W->head.qv, &act, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  if (W->head.kind != WIDE_RB) return wide_forward_q(W, params, src, 0, n, nullptr, W->head.qv, &act, st);
+  if (int rc = wide_forward_q(W, params, src, 0, n, noise, W->head.qv, nullptr, st)) return rc;
+  hipLaunchKernelGGL(rb_act_kernel, dim3((n + 63) / 64), dim3(64), 0, st, W->head.qv, n, W->A, act.out);
+  DQZ_HIP(hipGetLastError());
+  return DQZ_OK;
 }
 
 static int wide_check_options(const dqz_wide_options* opt) {
@@ -1365,16 +1413,22 @@ static int wide_debug_check(WideKind kind, int batch, unsigned request, const dq
   return check_step(&L, &P, &S, r);
 }
 
-static int c51_create(const dqz_learner_config* cfg, int num_atoms, const float* support,
-                      const dqz_wide_options* opt, dqz_c51** out) {
-  if (!cfg || !support || !out) return fail(DQZ_ERR_INVALID, "null argument");
-  if (int rc = wide_check_config(WIDE_C51, cfg, num_atoms)) return rc;
-  // the support, checked on the host (this call may synchronise; the step never does)
-  float z[C51_MAXN];
+// A categorical head's support (C51's, Rainbow's) copied to z and checked on the host (this call may synchronise;
+// the step never does); behind wide_check_config, so num_atoms <= C51_MAXN
+static int c51_check_support(const float* support, int num_atoms, float z[C51_MAXN]) {
   DQZ_HIP(hipMemcpy(z, support, sizeof(float) * num_atoms, hipMemcpyDefault));
   for (int i = 0; i < num_atoms; ++i)
     if (!std::isfinite(z[i]) || (i > 0 && !(z[i] > z[i - 1])))
       return fail(DQZ_ERR_INVALID, "support must be finite and strictly increasing (atom %d)", i);
+  return DQZ_OK;
+}
+
+static int c51_create(const dqz_learner_config* cfg, int num_atoms, const float* support,
+                      const dqz_wide_options* opt, dqz_c51** out) {
+  if (!cfg || !support || !out) return fail(DQZ_ERR_INVALID, "null argument");
+  if (int rc = wide_check_config(WIDE_C51, cfg, num_atoms)) return rc;
+  float z[C51_MAXN];
+  if (int rc = c51_check_support(support, num_atoms, z)) return rc;
   return wide_create(WIDE_C51, cfg, num_atoms, z, 0.f, opt, reinterpret_cast<dqz_wide**>(out));
 }
 
@@ -1426,30 +1480,30 @@ int dqz_c51_destroy(dqz_c51* C) { return wide_destroy(wide_of(C)); }
 int dqz_c51_learner(dqz_c51* C, dqz_learner** out) { return wide_learner(wide_of(C), out); }
 int dqz_c51_step(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, dqz_optimizer* o,
                  int32_t* count, void* stream) {
-  return wide_step(wide_of(C), P, S, slots, nullptr, o, count, stream);
+  return wide_step(wide_of(C), P, S, slots, nullptr, nullptr, o, count, stream);
 }
 int dqz_c51_step_w(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, const float* is_weights,
                    dqz_optimizer* o, int32_t* count, void* stream) {
   if (int rc = wide_check_weights(C, is_weights)) return rc;
-  return wide_step(wide_of(C), P, S, slots, is_weights, o, count, stream);
+  return wide_step(wide_of(C), P, S, slots, is_weights, nullptr, o, count, stream);
 }
 int dqz_c51_grad(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
                  void* stream) {
-  return wide_grad(wide_of(C), P, S, slots, nullptr, grad_out, stream);
+  return wide_grad(wide_of(C), P, S, slots, nullptr, nullptr, grad_out, stream);
 }
 int dqz_c51_grad_w(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, const float* is_weights,
                    float* grad_out, void* stream) {
   if (int rc = wide_check_weights(C, is_weights)) return rc;
-  return wide_grad(wide_of(C), P, S, slots, is_weights, grad_out, stream);
+  return wide_grad(wide_of(C), P, S, slots, is_weights, nullptr, grad_out, stream);
 }
 int dqz_c51_profile(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
                     int iters, float* phase_ms, void* stream) {
-  return wide_profile(wide_of(C), P, S, slots, nullptr, grad_out, iters, phase_ms, stream);
+  return wide_profile(wide_of(C), P, S, slots, nullptr, nullptr, grad_out, iters, phase_ms, stream);
 }
 int dqz_c51_profile_w(dqz_c51* C, const dqz_params* P, const dqz_store* S, const int32_t* slots,
                       const float* is_weights, float* grad_out, int iters, float* phase_ms, void* stream) {
   if (int rc = wide_check_weights(C, is_weights)) return rc;
-  return wide_profile(wide_of(C), P, S, slots, is_weights, grad_out, iters, phase_ms, stream);
+  return wide_profile(wide_of(C), P, S, slots, is_weights, nullptr, grad_out, iters, phase_ms, stream);
 }
 int dqz_c51_outputs(dqz_c51* C, float* logits_a, float* q_values, float* loss_b, float* loss, int32_t* a_star,
                     void* stream) {
@@ -1462,15 +1516,15 @@ int dqz_c51_debug(dqz_c51* C, float* logits, float* dlogits, void* stream) {
   return wide_debug(wide_of(C), logits, dlogits, stream);
 }
 int dqz_c51_forward(dqz_c51* C, const float* params, const uint8_t* states, int n, float* q_out, void* stream) {
-  return wide_forward(wide_of(C), params, states, n, q_out, stream);
+  return wide_forward(wide_of(C), params, states, n, nullptr, q_out, stream);
 }
 int dqz_c51_forward_slots(dqz_c51* C, const float* params, const dqz_store* S, const int32_t* slots, int n, int which,
                           float* q_out, void* stream) {
-  return wide_forward_slots(wide_of(C), params, S, slots, n, which, q_out, stream);
+  return wide_forward_slots(wide_of(C), params, S, slots, n, which, nullptr, q_out, stream);
 }
 int dqz_c51_act(dqz_c51* C, const float* params, const uint8_t* states, int n, double epsilon, uint64_t seed,
                 uint64_t counter, dqz_action* out, void* stream) {
-  return wide_act(wide_of(C), params, states, n, epsilon, seed, counter, out, stream);
+  return wide_act(wide_of(C), params, states, n, nullptr, epsilon, seed, counter, out, stream);
 }
 int dqz_c51_debug_check(int batch, unsigned request) { return wide_debug_check(WIDE_C51, batch, request, nullptr); }
 int dqz_c51_debug_check_opt(int batch, unsigned request, const dqz_wide_options* options) {
@@ -1488,30 +1542,30 @@ int dqz_qr_destroy(dqz_qr* Q) { return wide_destroy(wide_of(Q)); }
 int dqz_qr_learner(dqz_qr* Q, dqz_learner** out) { return wide_learner(wide_of(Q), out); }
 int dqz_qr_step(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, dqz_optimizer* o,
                 int32_t* count, void* stream) {
-  return wide_step(wide_of(Q), P, S, slots, nullptr, o, count, stream);
+  return wide_step(wide_of(Q), P, S, slots, nullptr, nullptr, o, count, stream);
 }
 int dqz_qr_step_w(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, const float* is_weights,
                    dqz_optimizer* o, int32_t* count, void* stream) {
   if (int rc = wide_check_weights(Q, is_weights)) return rc;
-  return wide_step(wide_of(Q), P, S, slots, is_weights, o, count, stream);
+  return wide_step(wide_of(Q), P, S, slots, is_weights, nullptr, o, count, stream);
 }
 int dqz_qr_grad(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
                 void* stream) {
-  return wide_grad(wide_of(Q), P, S, slots, nullptr, grad_out, stream);
+  return wide_grad(wide_of(Q), P, S, slots, nullptr, nullptr, grad_out, stream);
 }
 int dqz_qr_grad_w(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, const float* is_weights,
                    float* grad_out, void* stream) {
   if (int rc = wide_check_weights(Q, is_weights)) return rc;
-  return wide_grad(wide_of(Q), P, S, slots, is_weights, grad_out, stream);
+  return wide_grad(wide_of(Q), P, S, slots, is_weights, nullptr, grad_out, stream);
 }
 int dqz_qr_profile(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots, float* grad_out,
                    int iters, float* phase_ms, void* stream) {
-  return wide_profile(wide_of(Q), P, S, slots, nullptr, grad_out, iters, phase_ms, stream);
+  return wide_profile(wide_of(Q), P, S, slots, nullptr, nullptr, grad_out, iters, phase_ms, stream);
 }
 int dqz_qr_profile_w(dqz_qr* Q, const dqz_params* P, const dqz_store* S, const int32_t* slots,
                       const float* is_weights, float* grad_out, int iters, float* phase_ms, void* stream) {
   if (int rc = wide_check_weights(Q, is_weights)) return rc;
-  return wide_profile(wide_of(Q), P, S, slots, is_weights, grad_out, iters, phase_ms, stream);
+  return wide_profile(wide_of(Q), P, S, slots, is_weights, nullptr, grad_out, iters, phase_ms, stream);
 }
 int dqz_qr_outputs(dqz_qr* Q, float* theta, float* q_values, float* loss_b, float* loss, int32_t* a_star,
                    void* stream) {
@@ -1524,15 +1578,15 @@ int dqz_qr_debug(dqz_qr* Q, float* outputs, float* dtheta, void* stream) {
   return wide_debug(wide_of(Q), outputs, dtheta, stream);
 }
 int dqz_qr_forward(dqz_qr* Q, const float* params, const uint8_t* states, int n, float* q_out, void* stream) {
-  return wide_forward(wide_of(Q), params, states, n, q_out, stream);
+  return wide_forward(wide_of(Q), params, states, n, nullptr, q_out, stream);
 }
 int dqz_qr_forward_slots(dqz_qr* Q, const float* params, const dqz_store* S, const int32_t* slots, int n, int which,
                          float* q_out, void* stream) {
-  return wide_forward_slots(wide_of(Q), params, S, slots, n, which, q_out, stream);
+  return wide_forward_slots(wide_of(Q), params, S, slots, n, which, nullptr, q_out, stream);
 }
 int dqz_qr_act(dqz_qr* Q, const float* params, const uint8_t* states, int n, double epsilon, uint64_t seed,
                uint64_t counter, dqz_action* out, void* stream) {
-  return wide_act(wide_of(Q), params, states, n, epsilon, seed, counter, out, stream);
+  return wide_act(wide_of(Q), params, states, n, nullptr, epsilon, seed, counter, out, stream);
 }
 int dqz_qr_debug_check(int batch, unsigned request) { return wide_debug_check(WIDE_QR, batch, request, nullptr); }
 int dqz_qr_debug_check_opt(int batch, unsigned request, const dqz_wide_options* options) {
@@ -1545,29 +1599,16 @@ int dqz_qr_debug_check_opt(int batch, unsigned request, const dqz_wide_options* 
 // ---------------------------------------------------------------------------
 // the Rainbow agent (rainbow.hpp): a categorical head (double_q and weighted) behind the noisy dueling network
 
-// The wide handle plus what the noisy layers need.  Of the inner learner's buffers fc1p holds A1-mu's partials,
-// h1 is h_adv, dz1 is dz_adv and dy3 the combined dX, so the step's own fc1 dW and update find A1-mu as fc1.
-struct dqz_rainbow {
-  dqz_wide* W;
-  RbLeaves lf;
-  RbNoise nl;
-  int64_t off[DQZ_RAINBOW_NUM_LEAVES], sz[DQZ_RAINBOW_NUM_LEAVES], total;
-  const float* noise;  // the running call's: [3][len] of a step, [len] of a forward
-  float* ys;           // [2][Z][B][3136] e_in * y3 of A1 and of V1
-  float* part[3];      // [Z][S][B][512] split-K partials of V1-mu, A1-sigma, V1-sigma
-  float *h_val, *adv, *val;              // [Z][B][512], [Z][B][A N], [Z][B][N]
-  float *dz_val, *dz_adv_e, *dz_val_e;   // [B][512]
-  float* dx;                             // [4][B][3136]
-  void* block;
-};
+// A dqz_rainbow handle is a dqz_wide whose head is WIDE_RB and whose rb is the network (RbNet, above).
 
 // Everything between the torso's fc1 launch (A1-mu, in L->fc1p) and the head: q_logits of Z applications on B
-// rows into the head's `out`.
-static int rb_outputs(dqz_rainbow* R, const NetZ& nz, int Z, int B, hipStream_t st) {
-  dqz_learner* L = R->W->L;
-  const int A = R->W->A, N = R->W->N, AN = A * N;
+// rows under `noise` [Z][len] into the head's `out`.
+static int rb_outputs(dqz_learner* L, const WideHead& c, const NetZ& nz, int Z, int B, const float* noise,
+                      hipStream_t st) {
+  const RbNet* R = c.rb;
+  const int A = L->cfg.num_actions, N = c.N, AN = A * N;
   const int64_t rows = (int64_t)Z * B;
-  RbScaleArgs sc{L->y3, R->noise, R->nl, Z, B, R->ys};
+  RbScaleArgs sc{L->y3, noise, R->nl, Z, B, R->ys};
   hipLaunchKernelGGL(rb_scale_kernel, dim3((unsigned)((rows * (FLAT / 4) + 255) / 256)), dim3(256), 0, st, sc);
   DQZ_HIP(hipGetLastError());
   Fc1FwdArgs f = make_fwd_args(L, nz, Z, B, Conv1Src{}).f1;
@@ -1589,7 +1630,7 @@ static int rb_outputs(dqz_rainbow* R, const NetZ& nz, int Z, int B, hipStream_t 
   h.S = L->S_fc1;
   h.nz = nz;
   h.lf = R->lf;
-  h.noise = R->noise;
+  h.noise = noise;
   h.nl = R->nl;
   h.Z = Z;
   h.B = B;
@@ -1597,39 +1638,25 @@ static int rb_outputs(dqz_rainbow* R, const NetZ& nz, int Z, int B, hipStream_t 
   h.h_val = R->h_val;
   hipLaunchKernelGGL(rb_hidden_kernel, dim3((unsigned)((rows * HID + 255) / 256)), dim3(256), 0, st, h);
   DQZ_HIP(hipGetLastError());
-  RbLogitsArgs g{L->h1, R->h_val, nz, R->lf, R->noise, R->nl, Z, B, AN, N, R->adv, R->val};
+  RbLogitsArgs g{L->h1, R->h_val, nz, R->lf, noise, R->nl, Z, B, AN, N, R->adv, R->val};
   hipLaunchKernelGGL(rb_logits_kernel, dim3((AN + N + 255) / 256, (unsigned)rows), dim3(256), 0, st, g);
   DQZ_HIP(hipGetLastError());
-  RbCombineArgs c{R->adv, R->val, Z, B, A, N, R->W->head.out};
-  hipLaunchKernelGGL(rb_combine_kernel, dim3((unsigned)((rows * N + 255) / 256)), dim3(256), 0, st, c);
+  RbCombineArgs cm{R->adv, R->val, Z, B, A, N, c.out};
+  hipLaunchKernelGGL(rb_combine_kernel, dim3((unsigned)((rows * N + 255) / 256)), dim3(256), 0, st, cm);
   DQZ_HIP(hipGetLastError());
   return DQZ_OK;
 }
 
 static int rb_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, const StepRequest& r, hipStream_t st) {
   const WideHead& c = *r.wide;
-  dqz_rainbow* R = static_cast<dqz_rainbow*>(c.rb);
+  const RbNet* R = c.rb;
   const int B = L->cfg.batch, A = L->cfg.num_actions, N = c.N;
   if (which == WIDE_OUTPUTS) {
     const NetZ nz{{P->online, P->target, P->online}, {0, 1, 1}};
-    return rb_outputs(R, nz, L->Z, B, st);
+    return rb_outputs(L, c, nz, L->Z, B, r.noise, st);
   }
-  if (which == WIDE_HEAD) {
-    C51HeadArgs h = c51_head_args(c, L->Z, B, A);
-    h.rec = reinterpret_cast<const float4*>(L->rec);
-    h.qv = c.qv;
-    h.la = c.taken;
-    h.dl = c.dtaken;
-    h.astar = c.astar;
-    h.loss_part = L->loss_part;
-    h.gq = L->gq;
-    h.ga = L->ga;
-    h.weights = r.is_weights;
-    h.loss_b = c.loss_b;
-    h.prio = L->td;
-    hipLaunchKernelGGL(c51_head_kernel<WIDE_DOUBLE | WIDE_WEIGHTED | WIDE_NO_DZ1>, dim3(B), dim3(HID), 0, st, h);
-  } else if (which == WIDE_DZ1) {
-    RbDhiddenArgs d{c.dtaken, L->ga, L->h1, R->h_val, P->online, R->lf, R->noise, R->nl, B, A, N,
+  if (which == WIDE_DZ1) {
+    RbDhiddenArgs d{c.dtaken, L->ga, L->h1, R->h_val, P->online, R->lf, r.noise, R->nl, B, A, N,
                     L->dz1, R->dz_val, R->dz_adv_e, R->dz_val_e};
     hipLaunchKernelGGL(rb_dhidden_kernel, dim3(B, HID / RB_DH_ROWS), dim3(512), 0, st, d);
   } else if (which == WIDE_FC1_DX) {
@@ -1653,10 +1680,10 @@ static int rb_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, cons
       f.w2p = i == 0 ? L->w2p : nullptr;
       if (int rc = fc1_dx(f, st)) return rc;
     }
-    RbDxCombineArgs x{R->dx, R->noise, R->nl, B, L->dy3};
+    RbDxCombineArgs x{R->dx, r.noise, R->nl, B, L->dy3};
     hipLaunchKernelGGL(rb_dx_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x);
   } else {  // WIDE_FC2_GRAD: every fc leaf but A1-mu
-    RbFc2GradArgs g{c.dtaken, L->ga, L->h1, R->h_val, R->dz_val, R->dz_adv_e, R->dz_val_e, R->noise, R->nl, R->lf,
+    RbFc2GradArgs g{c.dtaken, L->ga, L->h1, R->h_val, R->dz_val, R->dz_adv_e, R->dz_val_e, r.noise, R->nl, R->lf,
                     B, A, N, r.gout, r.gacc};
     hipLaunchKernelGGL(rb_fc2_grad_kernel, dim3((unsigned)((rb_fc2_grad_elems(A * N, N) + 255) / 256)), dim3(256), 0,
                        st, g);
@@ -1669,21 +1696,46 @@ static int rb_launch(WideLaunch which, dqz_learner* L, const dqz_params* P, cons
   return DQZ_OK;
 }
 
-static dqz_wide* wide_of(dqz_rainbow* R) { return R ? R->W : nullptr; }
-
-// q_values of n states through one application of the network under `noise`
-static int rb_forward_q(dqz_rainbow* R, const float* params, const Conv1Src& src, int which, int n,
-                        const float* noise, float* q_out, hipStream_t st) {
-  dqz_wide* W = R->W;
-  if (reinterpret_cast<uintptr_t>(params) % 16) return fail(DQZ_ERR_INVALID, "parameters must be 16-byte aligned");
-  if (int rc = forward_torso(W->L, params, src, which, n, st)) return rc;
-  R->noise = noise;
-  const NetZ nz{{params, params, params}, {which, which, which}};
-  if (int rc = rb_outputs(R, nz, 1, n, st)) return rc;
-  C51HeadArgs h = c51_head_args(W->head, 1, n, W->A);
-  set_forward(&h, q_out, nullptr);
-  hipLaunchKernelGGL(c51_head_kernel<0>, dim3(n), dim3(HID), 0, st, h);
-  DQZ_HIP(hipGetLastError());
+// The noisy network of a WIDE_RB head fresh from wide_create: the twenty-leaf layout (the inner learner's too) and
+// the scratch.  On failure W, which owns what was made so far, is the caller's to destroy.
+static int rb_attach(dqz_wide* W) {
+  RbNet* R = new RbNet();
+  W->rb = R;
+  W->head.rb = R;
+  dqz_learner* L = W->L;
+  const int A = W->A, N = W->N;
+  rb_param_layout(A, N, R->off, R->sz, &R->total);
+  for (int i = 0; i < 10; ++i) {  // the step's view: leaves 0-7 (A1-mu as fc1); 8 and 9 it never touches behind a wide head
+    L->off[i] = R->off[i];
+    L->sz[i] = R->sz[i];
+  }
+  L->total = R->total;
+  const int64_t* o = R->off;
+  R->lf = RbLeaves{o[6], o[7], o[8], o[9], o[10], o[11], o[12], o[13], o[14], o[15], o[16], o[17], o[18], o[19]};
+  R->nl = rb_noise_layout(A, N);
+  const auto pad = [](int64_t n) { return (n + 63) / 64 * 64; };
+  const int64_t B = L->cfg.batch, Z = L->Z, AN = (int64_t)A * N;
+  const int64_t n_ys = pad(2 * Z * B * FLAT), n_part = pad(Z * L->S_fc1 * B * HID), n_h = pad(Z * B * HID);
+  const int64_t n_adv = pad(Z * B * AN), n_val = pad(Z * B * N), n_dz = pad(B * HID), n_dx = pad(4 * B * FLAT);
+  const int64_t floats = n_ys + 3 * n_part + n_h + n_adv + n_val + 3 * n_dz + n_dx;
+  if (hipMalloc(&R->block, floats * sizeof(float)) != hipSuccess ||
+      hipMemset(R->block, 0, floats * sizeof(float)) != hipSuccess)
+    return fail(DQZ_ERR_HIP, "hipMalloc of %lld bytes of rainbow scratch failed", (long long)(floats * 4));
+  float* p = (float*)R->block;
+  R->ys = p;
+  p += n_ys;
+  for (int i = 0; i < 3; ++i, p += n_part) R->part[i] = p;
+  R->h_val = p;
+  p += n_h;
+  R->adv = p;
+  p += n_adv;
+  R->val = p;
+  p += n_val;
+  R->dz_val = p;
+  R->dz_adv_e = p + n_dz;
+  R->dz_val_e = p + 2 * n_dz;
+  p += 3 * n_dz;
+  R->dx = p;
   return DQZ_OK;
 }
 
@@ -1720,10 +1772,7 @@ int dqz_rainbow_noise(uint64_t seed, uint64_t* counter_dev, int n, float* out, v
 }
 
 int dqz_rainbow_optimizer_create(const dqz_optimizer_config* cfg, int num_atoms, dqz_optimizer** out) {
-  if (!cfg || !out) return fail(DQZ_ERR_INVALID, "null argument");
-  if (int rc = wide_check_shape(WIDE_RB, cfg->num_actions, num_atoms)) return rc;
-  if (cfg->shared_bias) return fail(DQZ_ERR_INVALID, "the %s head has no shared bias", kWide[WIDE_RB].noun);
-  return optimizer_create(cfg, num_atoms, out, 1);
+  return wide_optimizer_create(WIDE_RB, cfg, num_atoms, out);
 }
 
 int dqz_rainbow_create(const dqz_learner_config* cfg, int num_atoms, const float* support,
@@ -1733,99 +1782,44 @@ int dqz_rainbow_create(const dqz_learner_config* cfg, int num_atoms, const float
     return fail(DQZ_ERR_INVALID, "the rainbow step is always double-Q and weighted: options must be {1, 1} or null");
   if (int rc = wide_check_config(WIDE_RB, cfg, num_atoms)) return rc;
   float z[C51_MAXN];
-  DQZ_HIP(hipMemcpy(z, support, sizeof(float) * num_atoms, hipMemcpyDefault));
-  for (int i = 0; i < num_atoms; ++i)
-    if (!std::isfinite(z[i]) || (i > 0 && !(z[i] > z[i - 1])))
-      return fail(DQZ_ERR_INVALID, "support must be finite and strictly increasing (atom %d)", i);
+  if (int rc = c51_check_support(support, num_atoms, z)) return rc;
   const dqz_wide_options both{1, 1};
   dqz_wide* W = nullptr;
   if (int rc = wide_create(WIDE_RB, cfg, num_atoms, z, 0.f, &both, &W)) return rc;
-  dqz_rainbow* R = new dqz_rainbow();
-  R->W = W;
-  W->head.rb = R;
-  dqz_learner* L = W->L;
-  const int A = cfg->num_actions, N = num_atoms;
-  rb_param_layout(A, N, R->off, R->sz, &R->total);
-  for (int i = 0; i < 10; ++i) {  // the step's view: leaves 0-7 (A1-mu as fc1); 8 and 9 it never touches behind a wide head
-    L->off[i] = R->off[i];
-    L->sz[i] = R->sz[i];
+  if (int rc = rb_attach(W)) {
+    (void)wide_destroy(W);  // it words no refusal: rb_attach's stands
+    return rc;
   }
-  L->total = R->total;
-  const int64_t* o = R->off;
-  R->lf = RbLeaves{o[6], o[7], o[8], o[9], o[10], o[11], o[12], o[13], o[14], o[15], o[16], o[17], o[18], o[19]};
-  R->nl = rb_noise_layout(A, N);
-  const auto pad = [](int64_t n) { return (n + 63) / 64 * 64; };
-  const int64_t B = cfg->batch, Z = L->Z, AN = (int64_t)A * N;
-  const int64_t n_ys = pad(2 * Z * B * FLAT), n_part = pad(Z * L->S_fc1 * B * HID), n_h = pad(Z * B * HID);
-  const int64_t n_adv = pad(Z * B * AN), n_val = pad(Z * B * N), n_dz = pad(B * HID), n_dx = pad(4 * B * FLAT);
-  const int64_t floats = n_ys + 3 * n_part + n_h + n_adv + n_val + 3 * n_dz + n_dx;
-  if (hipMalloc(&R->block, floats * sizeof(float)) != hipSuccess ||
-      hipMemset(R->block, 0, floats * sizeof(float)) != hipSuccess) {
-    if (R->block) (void)hipFree(R->block);
-    (void)wide_destroy(W);
-    delete R;
-    return fail(DQZ_ERR_HIP, "hipMalloc of %lld bytes of rainbow scratch failed", (long long)(floats * 4));
-  }
-  float* p = (float*)R->block;
-  R->ys = p;
-  p += n_ys;
-  for (int i = 0; i < 3; ++i, p += n_part) R->part[i] = p;
-  R->h_val = p;
-  p += n_h;
-  R->adv = p;
-  p += n_adv;
-  R->val = p;
-  p += n_val;
-  R->dz_val = p;
-  R->dz_adv_e = p + n_dz;
-  R->dz_val_e = p + 2 * n_dz;
-  p += 3 * n_dz;
-  R->dx = p;
-  *out = R;
+  *out = reinterpret_cast<dqz_rainbow*>(W);
   return DQZ_OK;
 }
 
-int dqz_rainbow_destroy(dqz_rainbow* R) {
-  if (!R) return DQZ_OK;
-  if (R->block) (void)hipFree(R->block);
-  (void)wide_destroy(R->W);
-  delete R;
-  return DQZ_OK;
-}
-
+int dqz_rainbow_destroy(dqz_rainbow* R) { return wide_destroy(wide_of(R)); }
 int dqz_rainbow_learner(dqz_rainbow* R, dqz_learner** out) { return wide_learner(wide_of(R), out); }
 
 int dqz_rainbow_step(dqz_rainbow* R, const dqz_params* P, const dqz_store* S, const int32_t* slots,
                      const float* is_weights, const float* noise, dqz_optimizer* o, int32_t* count, void* stream) {
   if (int rc = rb_check_step(R, is_weights, noise)) return rc;
-  R->noise = noise;
-  return wide_step(R->W, P, S, slots, is_weights, o, count, stream);
+  return wide_step(wide_of(R), P, S, slots, is_weights, noise, o, count, stream);
 }
-
 int dqz_rainbow_grad(dqz_rainbow* R, const dqz_params* P, const dqz_store* S, const int32_t* slots,
                      const float* is_weights, const float* noise, float* grad_out, void* stream) {
   if (int rc = rb_check_step(R, is_weights, noise)) return rc;
-  R->noise = noise;
-  return wide_grad(R->W, P, S, slots, is_weights, grad_out, stream);
+  return wide_grad(wide_of(R), P, S, slots, is_weights, noise, grad_out, stream);
 }
-
 int dqz_rainbow_profile(dqz_rainbow* R, const dqz_params* P, const dqz_store* S, const int32_t* slots,
                         const float* is_weights, const float* noise, float* grad_out, int iters, float* phase_ms,
                         void* stream) {
   if (int rc = rb_check_step(R, is_weights, noise)) return rc;
-  R->noise = noise;
-  return wide_profile(R->W, P, S, slots, is_weights, grad_out, iters, phase_ms, stream);
+  return wide_profile(wide_of(R), P, S, slots, is_weights, noise, grad_out, iters, phase_ms, stream);
 }
-
 int dqz_rainbow_outputs(dqz_rainbow* R, float* logits_a, float* q_values, float* loss_b, float* loss,
                         int32_t* a_star, void* stream) {
   return wide_outputs(wide_of(R), logits_a, q_values, loss_b, loss, a_star, stream);
 }
-
 int dqz_rainbow_outputs_opt(dqz_rainbow* R, float* q_selector, float* priorities, void* stream) {
   return wide_outputs_opt(wide_of(R), q_selector, priorities, stream);
 }
-
 int dqz_rainbow_debug_head(dqz_rainbow* R, float* q_logits, float* dlogits, void* stream) {
   return wide_debug(wide_of(R), q_logits, dlogits, stream);
 }
@@ -1834,14 +1828,16 @@ int dqz_rainbow_debug(dqz_rainbow* R, float* h_adv, float* h_val, float* adv, fl
                       float* dz_val, void* stream) {
   if (!R) return fail(DQZ_ERR_INVALID, "null argument");
   hipStream_t st = (hipStream_t)stream;
-  const dqz_learner* L = R->W->L;
-  const int64_t B = L->cfg.batch, AN = (int64_t)R->W->A * R->W->N;
+  const dqz_wide* W = wide_of(R);
+  const dqz_learner* L = W->L;
+  const RbNet* net = W->rb;
+  const int64_t B = L->cfg.batch, AN = (int64_t)W->A * W->N;
   const struct {
     float* dst;
     const float* src;
     int64_t n;
-  } rows[] = {{h_adv, L->h1, B * HID},    {h_val, R->h_val, B * HID},  {adv, R->adv, B * AN},
-              {val, R->val, B * R->W->N}, {dz_adv, L->dz1, B * HID},   {dz_val, R->dz_val, B * HID}};
+  } rows[] = {{h_adv, L->h1, B * HID},   {h_val, net->h_val, B * HID}, {adv, net->adv, B * AN},
+              {val, net->val, B * W->N}, {dz_adv, L->dz1, B * HID},    {dz_val, net->dz_val, B * HID}};
   for (const auto& r : rows)
     if (r.dst) DQZ_HIP(hipMemcpyAsync(r.dst, r.src, 4 * r.n, hipMemcpyDeviceToDevice, st));
   return DQZ_OK;
@@ -1850,31 +1846,17 @@ int dqz_rainbow_debug(dqz_rainbow* R, float* h_adv, float* h_val, float* adv, fl
 int dqz_rainbow_forward(dqz_rainbow* R, const float* params, const uint8_t* states, int n, const float* noise,
                         float* q_out, void* stream) {
   if (!R || !noise) return fail(DQZ_ERR_INVALID, "null argument");
-  Conv1Src src;
-  if (int rc = forward_src(R->W->L, params, n, {.states = states, .q_out = q_out}, &src)) return rc;
-  return rb_forward_q(R, params, src, 0, n, noise, q_out, (hipStream_t)stream);
+  return wide_forward(wide_of(R), params, states, n, noise, q_out, stream);
 }
-
 int dqz_rainbow_forward_slots(dqz_rainbow* R, const float* params, const dqz_store* S, const int32_t* slots, int n,
                               int which, const float* noise, float* q_out, void* stream) {
   if (!R || !noise) return fail(DQZ_ERR_INVALID, "null argument");
-  Conv1Src src;
-  const ForwardInput in{.from_store = true, .store = S, .slots = slots, .which = which, .q_out = q_out};
-  if (int rc = forward_src(R->W->L, params, n, in, &src)) return rc;
-  return rb_forward_q(R, params, src, which, n, noise, q_out, (hipStream_t)stream);
+  return wide_forward_slots(wide_of(R), params, S, slots, n, which, noise, q_out, stream);
 }
-
 int dqz_rainbow_act(dqz_rainbow* R, const float* params, const uint8_t* states, int n, const float* noise,
                     dqz_action* out, void* stream) {
   if (!R || !noise) return fail(DQZ_ERR_INVALID, "null argument");
-  ActorDraw act{0.0, 0, 0, out};  // no epsilon: forward_src's checks and device views of states and out
-  Conv1Src src;
-  if (int rc = forward_src(R->W->L, params, n, {.states = states, .act = &act}, &src)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = rb_forward_q(R, params, src, 0, n, noise, R->W->head.qv, st)) return rc;
-  hipLaunchKernelGGL(rb_act_kernel, dim3((n + 63) / 64), dim3(64), 0, st, R->W->head.qv, n, R->W->A, act.out);
-  DQZ_HIP(hipGetLastError());
-  return DQZ_OK;
+  return wide_act(wide_of(R), params, states, n, noise, 0.0, 0, 0, out, stream);  // no epsilon, no draw
 }
 
 int dqz_rainbow_debug_check(int batch, unsigned request) {

@@ -236,8 +236,10 @@ struct MetaSoftmax {
 // WIDE_RB is the categorical head behind the noisy dueling network of the Rainbow agent (rainbow.hpp): its loss,
 // projection, a* and priorities are the categorical head's with double_q and weighted both set, and the launches
 // around it (the other three fc1 products, both noisy fc2 layers, the dueling combine and their backward) are
-// wide_launch's as well.
+// wide_launch's as well.  They read the request's noise (StepRequest::noise) and the network's own leaves and
+// scratch, RbNet (learner.hip), which the head's handle owns.
 enum WideKind { WIDE_C51, WIDE_QR, WIDE_RB };
+struct RbNet;
 struct WideHead {
   WideKind kind;
   int N;              // atoms / quantiles per action
@@ -256,7 +258,7 @@ struct WideHead {
   int weighted;       // every step takes is_weights [B]; the head writes clip(|loss_b|, 0, 100) to the learner's td
   float* loss_b;      // [B] the unweighted per-sample loss of a weighted head (the learner's loss_part then holds
                       // w_b loss_b, what the update sums); null otherwise
-  void* rb;           // WIDE_RB alone: the dqz_rainbow that owns this head (learner.hip)
+  const RbNet* rb;    // WIDE_RB alone: the noisy dueling network in front of the head; null otherwise
 };
 constexpr int C51_MAX_ATOMS = 64, C51_MAX_OUT = 1024;     // c51.hpp's C51_MAXN / C51_MAXOUT
 constexpr int QR_MAX_QUANTILES = 256, QR_MAX_OUT = 4096;  // qr.hpp's QR_MAXN / QR_MAXOUT
@@ -310,8 +312,10 @@ struct StepRequest {
   const MetaSoftmax* meta_sm;  // the head forms p itself; meta_p is then its p_out
   uint8_t* xout;               // conv1 copies sample 0's s_tm1 bytes here (Conv1Src::xout)
   PhaseEvents pe;              // dqz_learner_profile: per-phase timing instead of one pass
-  // A wide head (C51 or QR-DQN): gradient mode only, batch from `slots`; check_step words what it refuses.
+  // A wide head (C51, QR-DQN or Rainbow): gradient mode only, batch from `slots`; check_step words what it refuses.
   const WideHead* wide;
+  const float* noise;  // [3][len] a WIDE_RB head's noise, one vector per network copy (rb_noise_layout's len);
+                       // the caller's for this call alone, read by no other head and not checked by check_step
 };
 
 // One of a wide head's launches of a learner step (learner.hip): the outputs of both copies (c51_logits_kernel,

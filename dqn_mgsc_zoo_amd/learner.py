@@ -471,6 +471,12 @@ class Learner:
 
   def q_values(self, states, params=None, stream=None):
     """network.apply(params, s).q_values for uint8 [n,84,84,4] device states."""
+    return self._forward(states, params, stream)
+
+  # The workers of q_values, q_values_slots and act: `extra` is what the
+  # head's entry takes between the inputs and the outputs.
+
+  def _forward(self, states, params, stream, *extra):
     params = self.online if params is None else params
     states = states.contiguous()
     n = int(states.shape[0])
@@ -480,8 +486,33 @@ class Learner:
       j = min(n, i + self.batch_size)
       _native.check(self._call(
           'forward', _native.ptr(params), _native.ptr(states[i:j]), j - i,
-          _native.ptr(out[i:j]), _native.stream_handle(stream)))
+          *extra, _native.ptr(out[i:j]), _native.stream_handle(stream)))
     return out
+
+  def _forward_slots(self, store, slots, which, params, stream, *extra):
+    params = self.online if params is None else params
+    n = int(slots.numel())
+    out = torch.empty((n, self.network.num_actions), dtype=torch.float32,
+                      device=self.device)
+    _native.check(self._call(
+        'forward_slots', _native.ptr(params), store.c_ref(), _native.ptr(slots),
+        n, int(which), *extra, _native.ptr(out), _native.stream_handle(stream)))
+    return out
+
+  def _forward_act(self, observation, params, *extra):
+    if self._act_in is None:
+      self._act_in = torch.empty((1, 84, 84, 4), dtype=torch.uint8,
+                                 pin_memory=True)
+      self._act_in_np = self._act_in.numpy()
+      self._act_out = torch.zeros((2,), dtype=torch.int32, pin_memory=True)
+      self._act_out_np = self._act_out.numpy()
+    self._act_in_np[0] = observation
+    _native.check(self._call(
+        'act', _native.ptr(self._params_tensor(params)),
+        ctypes.c_void_p(self._act_in.data_ptr()), 1, *extra,
+        ctypes.c_void_p(self._act_out.data_ptr()), _native.stream_handle()))
+    torch.cuda.current_stream(self.device).synchronize()
+    return int(self._act_out_np[0]), float(self._act_out_np.view(np.float32)[1])
 
   def _params_tensor(self, params):
     """Flat device parameters from None (online), a flat tensor, a device
@@ -520,30 +551,11 @@ class Learner:
     (dqz_act, dqz_c51_act).  The observation is read and the result written
     in place in pinned host buffers: one launch chain and one stream
     synchronisation per call, no staging copies."""
-    if self._act_in is None:
-      self._act_in = torch.empty((1, 84, 84, 4), dtype=torch.uint8,
-                                 pin_memory=True)
-      self._act_in_np = self._act_in.numpy()
-      self._act_out = torch.zeros((2,), dtype=torch.int32, pin_memory=True)
-      self._act_out_np = self._act_out.numpy()
-    self._act_in_np[0] = observation
-    _native.check(self._call(
-        'act', _native.ptr(self._params_tensor(params)),
-        ctypes.c_void_p(self._act_in.data_ptr()), 1, float(epsilon),
-        int(seed) & (2**64 - 1), int(counter) & (2**64 - 1),
-        ctypes.c_void_p(self._act_out.data_ptr()), _native.stream_handle()))
-    torch.cuda.current_stream(self.device).synchronize()
-    return int(self._act_out_np[0]), float(self._act_out_np.view(np.float32)[1])
+    return self._forward_act(observation, params, float(epsilon),
+                             int(seed) & (2**64 - 1), int(counter) & (2**64 - 1))
 
   def q_values_slots(self, store, slots, which, params=None, stream=None):
-    params = self.online if params is None else params
-    n = int(slots.numel())
-    out = torch.empty((n, self.network.num_actions), dtype=torch.float32,
-                      device=self.device)
-    _native.check(self._call(
-        'forward_slots', _native.ptr(params), store.c_ref(), _native.ptr(slots),
-        n, int(which), _native.ptr(out), _native.stream_handle(stream)))
-    return out
+    return self._forward_slots(store, slots, which, params, stream)
 
 
 def sample_uniform(base, size, capacity, n, seed, counter, out, stream=None):
@@ -672,25 +684,53 @@ class _WideLearner(Learner):
       raise ValueError('weights must be a device float32 tensor of batch size')
     return '_w', (_native.ptr(slots), _native.ptr(weights))
 
+  def _run(self, entry, store, slots, weights, extra, tail, stream):
+    """The worker of step, grad and profile: the head's `entry` (its _w twin
+    in a prioritized learner) on the batch, what the head takes behind the
+    weights (`extra`, checked by _extra_args behind slots and weights) and the
+    entry's own last arguments (`tail`)."""
+    suffix, args = self._weighted_args(slots, weights)
+    _native.check(self._call(
+        entry + suffix, ctypes.byref(self._params_c), store.c_ref(), *args,
+        *self._extra_args(*extra), *tail, _native.stream_handle(stream)))
+
+  def _extra_args(self):
+    """The head's own step inputs, checked, as the entry's arguments."""
+    return ()
+
+  def _profile(self, store, slots, weights, extra, iters, stream):
+    """profile's body: the gradient goes to a scratch tensor, the average ms
+    per launch come back under the head's own names."""
+    scratch = torch.zeros_like(self.online)
+    ms = (ctypes.c_float * _native.NUM_PHASES)()
+    self._run('profile', store, slots, weights, extra,
+              (_native.ptr(scratch), int(iters), ms), stream)
+    names = list(_native.PHASE_NAMES)
+    for slot, name in self._PROFILE_SLOTS.items():
+      names[slot] = name
+    return {n: float(t) for n, t in zip(names, ms) if t > 0.0}
+
   def step(self, store, slots, weights=None, stream=None):  # pylint: disable=arguments-differ
     """One learner step on replay `slots` (device int32 [B]); a prioritized
     learner's also takes the importance `weights` (device f32 [B])."""
-    suffix, args = self._weighted_args(slots, weights)
-    _native.check(self._call(
-        'step' + suffix, ctypes.byref(self._params_c), store.c_ref(), *args,
-        self._opt_h, _native.ptr(self.count), _native.stream_handle(stream)))
+    self._run('step', store, slots, weights, (),
+              (self._opt_h, _native.ptr(self.count)), stream)
 
   def grad(self, store, slots, weights=None, out=None, stream=None):  # pylint: disable=arguments-differ
     """jax.grad(loss_fn) of the same step into a flat tensor (no update).
     Every element of every leaf is written; the padding floats between the
     leaves and behind the last keep what `out` held (zeros in the tensor
     allocated here)."""
-    suffix, args = self._weighted_args(slots, weights)
     out = torch.zeros_like(self.online) if out is None else out
-    _native.check(self._call(
-        'grad' + suffix, ctypes.byref(self._params_c), store.c_ref(), *args,
-        _native.ptr(out), _native.stream_handle(stream)))
+    self._run('grad', store, slots, weights, (), (_native.ptr(out),), stream)
     return out
+
+  def apply(self, grad, stream=None):
+    """The optimizer on a finished gradient (what step does behind grad)."""
+    _native.check(_native.lib().dqz_optimizer_apply(
+        self._opt_h, _native.ptr(self.online), _native.ptr(grad),
+        _native.ptr(self.mu), _native.ptr(self.nu), _native.ptr(self.count),
+        _native.stream_handle(stream)))
 
   def fetch_outputs(self, stream=None):
     """(outputs of the taken action [B,N], q_values [2,B,A] of online(s_tm1)
@@ -727,17 +767,7 @@ class _WideLearner(Learner):
   def profile(self, store, slots, weights=None, iters=20, stream=None):  # pylint: disable=arguments-differ
     """Average ms per launch (the head's profile entry), dict; the gradient
     goes to a scratch tensor and no parameter changes."""
-    suffix, args = self._weighted_args(slots, weights)
-    out = (ctypes.c_float * _native.NUM_PHASES)()
-    scratch = torch.zeros_like(self.online)
-    _native.check(self._call(
-        'profile' + suffix, ctypes.byref(self._params_c), store.c_ref(),
-        *args, _native.ptr(scratch), int(iters), out,
-        _native.stream_handle(stream)))
-    names = list(_native.PHASE_NAMES)
-    for slot, name in self._PROFILE_SLOTS.items():
-      names[slot] = name
-    return {n: float(t) for n, t in zip(names, out) if t > 0.0}
+    return self._profile(store, slots, weights, (), iters, stream)
 
   def _no_fused_draw(self, *unused_args, **unused_kwargs):
     raise NotImplementedError(
@@ -783,11 +813,14 @@ class RainbowLearner(_WideLearner):
   the device counter, so equal (seed, counter) give equal bits.  Its tensors
   of the head: `support` [N] and `logits_a` [B,N]."""
 
+  # always prioritized: its one step, grad and profile are the weighted ones
   _ENTRIES = dict(
       {e: 'dqz_rainbow_' + e for e in (
-          'learner', 'optimizer_create', 'destroy', 'step', 'grad', 'outputs',
-          'profile', 'forward', 'forward_slots', 'act', 'outputs_opt')},
-      create_opt='dqz_rainbow_create', debug='dqz_rainbow_debug_head')
+          'learner', 'optimizer_create', 'destroy', 'outputs', 'forward',
+          'forward_slots', 'act', 'outputs_opt')},
+      create_opt='dqz_rainbow_create', debug='dqz_rainbow_debug_head',
+      step_w='dqz_rainbow_step', grad_w='dqz_rainbow_grad',
+      profile_w='dqz_rainbow_profile')
   _CLASS, _NETWORK = 'RainbowLearner', 'rainbow_atari_network'
   _SPEC = networks_lib.RainbowNetworkSpec
   _COUNT, _GRID, _TAKEN = 'num_atoms', 'support', 'logits_a'
@@ -829,48 +862,27 @@ class RainbowLearner(_WideLearner):
                        '%d x noise_len (%d) floats'
                        % (applications, self.noise_len))
 
-  def _step_args(self, slots, weights, noise):
-    suffix, args = self._weighted_args(slots, weights)
-    del suffix  # always weighted: one entry
+  def _extra_args(self, noise):  # pylint: disable=arguments-differ
+    """A step's noise [3, noise_len], checked behind slots and weights."""
     self._check_noise(noise, 3)
-    return args + (_native.ptr(noise),)
+    return (_native.ptr(noise),)
 
   def step(self, store, slots, weights=None, noise=None, stream=None):  # pylint: disable=arguments-differ
     """One learner step on `slots` with importance `weights` [B] under
     `noise` [3, noise_len]."""
-    _native.check(self._call(
-        'step', ctypes.byref(self._params_c), store.c_ref(),
-        *self._step_args(slots, weights, noise), self._opt_h,
-        _native.ptr(self.count), _native.stream_handle(stream)))
+    self._run('step', store, slots, weights, (noise,),
+              (self._opt_h, _native.ptr(self.count)), stream)
 
   def grad(self, store, slots, weights=None, noise=None, out=None, stream=None):  # pylint: disable=arguments-differ
     """The step's gradient into a flat tensor (no update); padding floats keep
     what `out` held."""
-    args = self._step_args(slots, weights, noise)
     out = torch.zeros_like(self.online) if out is None else out
-    _native.check(self._call(
-        'grad', ctypes.byref(self._params_c), store.c_ref(), *args,
-        _native.ptr(out), _native.stream_handle(stream)))
+    self._run('grad', store, slots, weights, (noise,), (_native.ptr(out),),
+              stream)
     return out
 
-  def apply(self, grad, stream=None):
-    """The optimizer on a finished gradient (what step does behind grad)."""
-    _native.check(_native.lib().dqz_optimizer_apply(
-        self._opt_h, _native.ptr(self.online), _native.ptr(grad),
-        _native.ptr(self.mu), _native.ptr(self.nu), _native.ptr(self.count),
-        _native.stream_handle(stream)))
-
   def profile(self, store, slots, weights=None, noise=None, iters=20, stream=None):  # pylint: disable=arguments-differ
-    args = self._step_args(slots, weights, noise)
-    out = (ctypes.c_float * _native.NUM_PHASES)()
-    scratch = torch.zeros_like(self.online)
-    _native.check(self._call(
-        'profile', ctypes.byref(self._params_c), store.c_ref(), *args,
-        _native.ptr(scratch), int(iters), out, _native.stream_handle(stream)))
-    names = list(_native.PHASE_NAMES)
-    for slot, name in self._PROFILE_SLOTS.items():
-      names[slot] = name
-    return {n: float(t) for n, t in zip(names, out) if t > 0.0}
+    return self._profile(store, slots, weights, (noise,), iters, stream)
 
   def fetch_noisy(self, stream=None):
     """Diagnostic: application 0's (h_adv, h_val [B,512], adv [B,A,N], val
@@ -886,47 +898,23 @@ class RainbowLearner(_WideLearner):
 
   def q_values(self, states, noise=None, params=None, stream=None):  # pylint: disable=arguments-differ
     """q_values [n,A] of uint8 [n,84,84,4] device states under one
-    application's `noise` [noise_len] (n <= batch size)."""
+    application's `noise` [noise_len].  n may exceed the batch size: the
+    states then go through in batch-size chunks, every chunk under the same
+    noise vector, which is the reference's single application over a whole
+    batch."""
     self._check_noise(noise, 1)
-    params = self.online if params is None else params
-    states = states.contiguous()
-    n = int(states.shape[0])
-    out = torch.empty((n, self.network.num_actions), dtype=torch.float32,
-                      device=self.device)
-    _native.check(self._call(
-        'forward', _native.ptr(params), _native.ptr(states), n,
-        _native.ptr(noise), _native.ptr(out), _native.stream_handle(stream)))
-    return out
+    return self._forward(states, params, stream, _native.ptr(noise))
 
   def q_values_slots(self, store, slots, which, noise=None, params=None, stream=None):  # pylint: disable=arguments-differ
     self._check_noise(noise, 1)
-    params = self.online if params is None else params
-    n = int(slots.numel())
-    out = torch.empty((n, self.network.num_actions), dtype=torch.float32,
-                      device=self.device)
-    _native.check(self._call(
-        'forward_slots', _native.ptr(params), store.c_ref(), _native.ptr(slots),
-        n, int(which), _native.ptr(noise), _native.ptr(out),
-        _native.stream_handle(stream)))
-    return out
+    return self._forward_slots(store, slots, which, params, stream,
+                               _native.ptr(noise))
 
   def act(self, observation, noise, params=None):  # pylint: disable=arguments-differ
     """(argmax_a q, max_a q) of one host uint8 [84,84,4] observation under
     `noise` [noise_len]: no epsilon (rainbow/agent.py: the noise explores)."""
     self._check_noise(noise, 1)
-    if self._act_in is None:
-      self._act_in = torch.empty((1, 84, 84, 4), dtype=torch.uint8,
-                                 pin_memory=True)
-      self._act_in_np = self._act_in.numpy()
-      self._act_out = torch.zeros((2,), dtype=torch.int32, pin_memory=True)
-      self._act_out_np = self._act_out.numpy()
-    self._act_in_np[0] = observation
-    _native.check(self._call(
-        'act', _native.ptr(self._params_tensor(params)),
-        ctypes.c_void_p(self._act_in.data_ptr()), 1, _native.ptr(noise),
-        ctypes.c_void_p(self._act_out.data_ptr()), _native.stream_handle()))
-    torch.cuda.current_stream(self.device).synchronize()
-    return int(self._act_out_np[0]), float(self._act_out_np.view(np.float32)[1])
+    return self._forward_act(observation, params, _native.ptr(noise))
 
 
 def check_huber_param(huber_param):

@@ -36,16 +36,21 @@ class PrioritizedWideMixin:
     else:
       self._replay.add(transition, priority=self._max_seen_priority)
 
+  def _step_extra(self):
+    """What this agent's learner step takes behind the weights, made ready
+    between the sample and the step (Rainbow: its noise)."""
+    return ()
+
   def _learn(self) -> None:
     if self._replay.on_device:
       indices, slots, weights = self._replay.sample_device(
           self._batch_size, out=self._sample_out)
-      self._learner.step(self._store(), slots, weights)
+      self._learner.step(self._store(), slots, weights, *self._step_extra())
       self._replay.write_back(self._learner, indices, self._max_seen_dev)
       return
     ids, slots, weights = self._replay.sample_slots(self._batch_size)
     self._w.copy_(torch.from_numpy(np.asarray(weights, np.float32)))
-    self._learner.step(self._store(), slots, self._w)
+    self._learner.step(self._store(), slots, self._w, *self._step_extra())
     priorities = self._learner.fetch_outputs()[-1].cpu().numpy().astype(np.float64)
     self._max_seen_priority = max(self._max_seen_priority, float(priorities.max()))
     self._replay.update_priorities(ids, priorities)

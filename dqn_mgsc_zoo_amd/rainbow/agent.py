@@ -16,7 +16,6 @@ here; the distribution is the reference's.)
 
 from typing import Any
 
-import numpy as np
 import torch
 
 from dqn_mgsc_zoo_amd import learner as learner_lib
@@ -62,21 +61,10 @@ class Rainbow(prioritized_wide.PrioritizedWideMixin, c51_agent.C51):
     self._statistics['state_value'] = v
     return parts.Action(a)
 
-  def _learn(self) -> None:
-    lrn = self._learner
-    noise = lrn.make_noise(self._act_seed, self._noise_counter, 3, out=self._learn_noise)
-    if self._replay.on_device:
-      indices, slots, weights = self._replay.sample_device(
-          self._batch_size, out=self._sample_out)
-      lrn.step(self._store(), slots, weights, noise)
-      self._replay.write_back(lrn, indices, self._max_seen_dev)
-      return
-    ids, slots, weights = self._replay.sample_slots(self._batch_size)
-    self._w.copy_(torch.from_numpy(np.asarray(weights, np.float32)))
-    lrn.step(self._store(), slots, self._w, noise)
-    priorities = lrn.fetch_outputs()[-1].cpu().numpy().astype(np.float64)
-    self._max_seen_priority = max(self._max_seen_priority, float(priorities.max()))
-    self._replay.update_priorities(ids, priorities)
+  def _step_extra(self):
+    """A learn's three noise vectors, drawn behind the sample."""
+    return (self._learner.make_noise(self._act_seed, self._noise_counter, 3,
+                                     out=self._learn_noise),)
 
   @property
   def noise_counter(self) -> int:

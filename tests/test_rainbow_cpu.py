@@ -1,7 +1,11 @@
 """The Rainbow network's reference and spec, without a GPU: tests/rainbow_ref
 against torch autograd written in the reference's own order (mu(x) +
 sigma(e_in x) e_out), the dueling combine's known answers, and
-networks.rainbow_atari_network's leaves, sizes and initialisation."""
+networks.rainbow_atari_network's leaves, sizes and initialisation; and what
+the dqz_rainbow_* entries refuse of a handle that is not one, before any device
+call."""
+
+import ctypes
 
 import numpy as np
 import pytest
@@ -141,3 +145,57 @@ def test_sigma_init_is_the_constant_and_mu_is_bounded():
   back = net.unflatten(flat)
   for mod, name in net.leaf_paths():
     np.testing.assert_array_equal(back[mod][name], tree[mod][name])
+
+
+# -- refusals before any device call -------------------------------------------
+# tests/test_c51_cpu.py's pattern: the handle is the address of one zero word
+# (a dqz_wide whose learner is null), parameters and store have every pointer
+# null.  No entry may read or write the handle past that word.
+
+@pytest.fixture(scope='module')
+def lib():
+  import os  # pylint: disable=g-import-not-at-top
+  from dqn_mgsc_zoo_amd import _native  # pylint: disable=g-import-not-at-top
+  if not os.path.exists(_native.LIB_PATH):
+    import __graft_entry__  # pylint: disable=g-import-not-at-top
+    __graft_entry__._compile_lib()  # pylint: disable=protected-access
+  return _native.lib()
+
+
+INVALID = -1
+_WORD = ctypes.c_int64(0)
+P = ctypes.cast(ctypes.pointer(_WORD), ctypes.c_void_p)  # any non-null address
+_OUT = ctypes.byref(ctypes.c_void_p())
+
+_REFUSALS = [
+    ('step-null-handle', ('step', (None, 'PARAMS', 'STORE', P, P, P, P, P, None)), 'null argument'),
+    ('step-null-weights', ('step', (P, 'PARAMS', 'STORE', P, None, P, P, P, None)), 'null argument'),
+    ('step-null-noise', ('step', (P, 'PARAMS', 'STORE', P, P, None, P, P, None)), 'null argument'),
+    ('step-null-optimizer', ('step', (P, 'PARAMS', 'STORE', P, P, P, None, P, None)), 'null argument'),
+    ('step-fake-optimizer', ('step', (P, 'PARAMS', 'STORE', P, P, P, P, P, None)), 'null optimizer state'),
+    ('grad-null-handle', ('grad', (None, 'PARAMS', 'STORE', P, P, P, P, None)), 'null argument'),
+    ('grad-null-out', ('grad', (P, 'PARAMS', 'STORE', P, P, P, None, None)), 'null grad_out'),
+    ('profile-null-phase-ms', ('profile', (P, 'PARAMS', 'STORE', P, P, P, P, 1, None, None)),
+     'phase_ms must be non-null'),
+    ('forward-null-handle', ('forward', (None, P, P, 1, P, P, None)), 'null argument'),
+    ('forward-null-states', ('forward', (P, P, None, 1, P, P, None)), 'null argument'),
+    ('forward-null-noise', ('forward', (P, P, P, 1, None, P, None)), 'null argument'),
+    ('forward-slots-null-slots', ('forward_slots', (P, P, 'STORE', None, 1, 0, P, P, None)), 'null argument'),
+    ('act-null-out', ('act', (P, P, P, 1, P, None, None)), 'null argument'),
+    ('learner-null-handle', ('learner', (None, _OUT)), 'null argument'),
+    ('outputs-null-handle', ('outputs', (None, P, P, P, P, P, None)), 'null argument'),
+    ('outputs-opt-null-handle', ('outputs_opt', (None, P, P, None)), 'null argument'),
+    ('debug-head-null-handle', ('debug_head', (None, P, P, None)), 'null argument'),
+    ('debug-null-handle', ('debug', (None, P, P, P, P, P, P, None)), 'null argument'),
+]
+
+
+@pytest.mark.parametrize('call,fragment', [r[1:] for r in _REFUSALS], ids=[r[0] for r in _REFUSALS])
+def test_refused_before_any_device_call(lib, call, fragment):
+  from dqn_mgsc_zoo_amd import _native  # pylint: disable=g-import-not-at-top
+  params, store = _native.DqzParams(), _native.DqzStore()  # every pointer null
+  named = {'PARAMS': ctypes.byref(params), 'STORE': ctypes.byref(store)}
+  entry, args = call
+  args = [named.get(x, x) if isinstance(x, str) else x for x in args]
+  assert getattr(lib, 'dqz_rainbow_' + entry)(*args) == INVALID
+  assert fragment.encode() in lib.dqz_last_error(), lib.dqz_last_error()

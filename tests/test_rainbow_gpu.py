@@ -561,6 +561,74 @@ def test_actor(device):
     np.testing.assert_allclose(q_host, q_ref[i], atol=1e-4 * zmax)
 
 
+def _small(device):
+  """B = 5, A = 3, N = 7: (learner, store, (slots, weights, noise [3, len]),
+  the batch's s_t stacks [B,84,84,4], another three noise vectors)."""
+  case = _case(5, 3, 7)
+  lrn, st = _device(case, device)
+  host = case['host']
+  s_t = helpers.stacks_from(host['frames'], host['fidx'], case['slots'], 1)
+  other = rainbow_ref.make_noise(np.random.default_rng(11), 3, 3, 7)
+  assert not np.array_equal(other, case['noise'])
+  return lrn, st, _args(case, device), s_t, torch.from_numpy(other).to(device)
+
+
+def test_profile_names_the_noisy_networks_launches(device):
+  """profile() reports the noisy network's launches under their own names, in
+  place of the C51 and QR-DQN ones, and changes no state."""
+  from dqn_mgsc_zoo_amd import learner as learner_lib
+  lrn, st, (slots, weights, noise), _, _ = _small(device)
+  state = (lrn.online, lrn.target, lrn.mu, lrn.nu, lrn.count)
+  before = [_bits(t) for t in state]
+  ms = lrn.profile(st, slots, weights, noise, iters=2)
+  torch.cuda.synchronize()
+  print(sorted(ms))
+  own = {'rb_noisy_forward', 'c51_head', 'rb_dhidden', 'rb_fc1_dx', 'rb_fc_grad'}
+  assert own == set(learner_lib.RainbowLearner._PROFILE_SLOTS.values())  # pylint: disable=protected-access
+  assert own <= set(ms)
+  replaced = set()
+  for other in (learner_lib.C51Learner, learner_lib.QrLearner):
+    replaced |= set(other._PROFILE_SLOTS.values()) - own  # pylint: disable=protected-access
+  assert len(replaced) == 6 and not replaced & set(ms)
+  assert set(ms) == own | {
+      'conv1_fwd', 'fc1_fwd', 'conv3_dx+conv2_dx+fc1_dw+conv3_dw+conv2_dw+conv1_dw', 'update'}
+  for t, b in zip(state, before):
+    assert np.array_equal(_bits(t), b)
+  assert lrn.sync_status() == 0
+
+
+def test_noise_belongs_to_the_call(device):
+  """No call leaves its noise behind for a later one: a gradient under one
+  noise has the same bits before and after forwards and an actor call under
+  others, and a forward the same bits before and after a gradient."""
+  lrn, st, (slots, weights, noise_a), s_t, other = _small(device)
+  states = torch.from_numpy(s_t).to(device)
+  grad_a = _bits(lrn.grad(st, slots, weights, noise_a))
+  q_b = _bits(lrn.q_values(states, other[0]))
+  lrn.q_values_slots(st, slots, 1, other[1])
+  lrn.act(s_t[0], other[2])
+  assert np.array_equal(_bits(lrn.grad(st, slots, weights, noise_a)), grad_a)
+  assert np.array_equal(_bits(lrn.q_values(states, other[0])), q_b)
+  # the noise is read: other vectors, other bits
+  assert not np.array_equal(_bits(lrn.grad(st, slots, weights, other)), grad_a)
+  assert not np.array_equal(_bits(lrn.q_values(states, other[1])), q_b)
+  assert lrn.sync_status() == 0
+
+
+def test_q_values_in_chunks(device):
+  """q_values of 2B - 1 states under one noise vector is the calls on [0, B)
+  and [B, 2B - 1) side by side, bit for bit."""
+  lrn, _, _, s_t, other = _small(device)
+  b = s_t.shape[0]
+  states = torch.from_numpy(np.concatenate([s_t, s_t[::-1][:b - 1]])).to(device)
+  assert states.shape[0] == 2 * b - 1
+  whole = lrn.q_values(states, other[0])
+  parts = torch.cat([lrn.q_values(states[:b], other[0]), lrn.q_values(states[b:], other[0])])
+  assert whole.shape == (2 * b - 1, 3)
+  assert np.array_equal(_bits(whole), _bits(parts))
+  assert not np.array_equal(_bits(whole[:b - 1]), _bits(whole[b:]))  # other states behind the first chunk
+
+
 def test_refusals_and_limits(device):
   from dqn_mgsc_zoo_amd import _native
   from dqn_mgsc_zoo_amd import learner as learner_lib
@@ -622,6 +690,11 @@ def test_refusals_and_limits(device):
     lrn.step(st, slots, None, noise)
   with pytest.raises(ValueError, match='noise'):
     lrn.step(st, slots, weights, noise[:2])
+  for call in (lrn.step, lrn.grad, lrn.profile):  # weights are refused before noise, noise by every entry
+    with pytest.raises(ValueError, match='importance weights'):
+      call(st, slots, None, noise[:2])
+    with pytest.raises(ValueError, match='noise'):
+      call(st, slots, weights, noise[:2])
   with pytest.raises(NotImplementedError, match='takes its batch as slots'):
     lrn.step_uniform()
   # an optimizer of another layout is refused before anything runs
